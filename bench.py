@@ -18,6 +18,10 @@ Workloads (BASELINE.json `configs`):
   c2: configs[1], Whisper-base -> Llama-3-8B, LoRA r16, batch 8 x 30 s;
   c4: configs[3], HuBERT-large -> Vicuna-7B, Q-Former (32 queries, 8 layers), LoRA r32, batch 6 x 30 s raw waveforms.
 Weak scaling: per-GPU work is fixed as N grows; no data-path collective except the gradient all-reduce.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the JSON line.  `--full` adds what
+takes time or perturbs the step beyond that: per-launch HIP events on sampled timed steps (`kernels`, `roofline`) and the CPU leg
+(`cpu_baseline`, unless --no-cpu-baseline).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -28,8 +32,10 @@ import os
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 import socket
 import statistics
+import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -256,7 +262,8 @@ def self_launch(args):
         env["SLAM_DIST_BACKEND"] = "gloo"   # ranks share a device: RCCL cannot, gloo can (functional check only)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    # a child process, not an exec: this process has already initialised the HIP runtime (device_count above)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def traffic_for(kernel_name):
@@ -331,12 +338,80 @@ def throughput(world: int, n_clips: int, clip_s: float, steps: int, elapsed: flo
     return world * n_clips * clip_s * steps / elapsed, elapsed / steps * 1e3
 
 
+def kernel_figures(ksum, n_timed, steps, ms_per_step, workload):
+    """--full: per-kernel table and roofline of the dominant GEMM instance from the per-launch HIP events of the sampled timed steps"""
+    gemm_all = [v for k, v in ksum.items() if k.startswith("gemm_nt")]
+    gemm_ms = sum(v["total_ms"] for v in gemm_all)
+    gemm_tf_all = sum(v["work"] for v in gemm_all) / (gemm_ms * 1e-3) / 1e12
+    dom = max((k for k in ksum if k.startswith("gemm_nt")), key=lambda k: ksum[k]["total_ms"])
+    g = ksum[dom]  # the dominant kernel (largest share of the step): one template instance of the bf16 GEMM
+    gemm_tf = g["work"] / (g["total_ms"] * 1e-3) / 1e12
+    kern = {k: dict(launches_per_step=v["launches"] / n_timed, ms_per_step=v["total_ms"] / n_timed,
+                    avg_ms=v["avg_ms"], TFLOPs=v["work"] / (v["total_ms"] * 1e-3) / 1e12,
+                    **({"algorithmic_GB_per_launch": v["bytes"] / v["launches"] / 1e9} if v.get("bytes") else {}))
+            for k, v in ksum.items()}
+    traffic, traffic_src = (traffic_for(dom) if workload == "c3" else (None, None))
+    roof = {"bound": "mfma", "kernel": dom + " (slam_gemm_bf16_nt)", "achieved": gemm_tf,
+            "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_BF16_TFLOPS, "traffic": None,
+            "avg_launch_ms": g["avg_ms"], "launches_per_step": g["launches"] / n_timed,
+            "share_of_step": g["total_ms"] / n_timed / ms_per_step,
+            "timing": f"HIP events around every launch on {n_timed} of the {steps} timed steps (every {KERNEL_TIMING_EVERY}th, from the first): "
+                      f"~1 170 events per step cost it 0.9 %, so they are not recorded on every step",
+            "algorithmic_bytes_per_launch": g["bytes"] / g["launches"] if g.get("bytes") else None,
+            "all_gemm_instances": {"achieved": gemm_tf_all, "share_of_step": gemm_ms / n_timed / ms_per_step}}
+    pmc = pmc_for(dom) if workload == "c3" else None
+    if pmc is not None:
+        # MFMA-busy cycles / (active cycles x 256 CUs x 4 SIMDs) of the dominant kernel, longest-running shape first; at the clock the
+        # chip sustained under that kernel (power-limited: 1.55-1.78 GHz of 2.4), the same kernel's TFLOP/s = mfma_util x 2.5 PF x clock / 2.4
+        big = max(pmc["per_shape"].values(), key=lambda v: v["duration_us"])
+        roof["mfma_util"] = big["mfma_util"]
+        roof["effective_clock_GHz"] = big["effective_clock_GHz"]
+        roof["pmc_detail"] = pmc
+    if traffic is not None:
+        hbm = traffic["fetch_bytes_per_launch"] + traffic["write_bytes_per_launch"]
+        roof["traffic"] = hbm
+        roof["traffic_detail"] = dict(traffic, unit="bytes per launch (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE)", source=traffic_src,
+                                      ratio_to_algorithmic=(hbm / roof["algorithmic_bytes_per_launch"]) if roof["algorithmic_bytes_per_launch"] else None)
+    return roof, kern
+
+
+DUMP_SAMPLE_PER_TENSOR = 16384
+DUMP_SAMPLE_TOTAL = 8 << 20      # float32 elements over all parameters: 32 MB
+
+
+def dump_outputs(path, model, loss, acc):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files under `path` (two builds compared output
+    for output).  loss.npy / acc.npy = the step's return values; params_sample.npy = the trainable fp32 master parameters after its
+    optimizer update, in sorted name order: the whole tensor when it is small, else a fixed sample of its elements (indices seeded by the
+    parameter's name, so they do not depend on which other parameters exist)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "acc.npy"), torch.as_tensor(acc).detach().float().cpu().numpy())
+    params = model.store.params
+    cap = max(1, min(DUMP_SAMPLE_PER_TENSOR, DUMP_SAMPLE_TOTAL // max(1, len(params))))
+    parts = []
+    for name in sorted(params):
+        flat = params[name].detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(parts).numpy() if parts else np.zeros(0, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the figures a plain run leaves out: per-launch HIP events on every "
+                    f"{KERNEL_TIMING_EVERY}th timed step (`kernels`, `roofline`) and the CPU leg (`cpu_baseline`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as "
+                    "DIR/<name>.npy (float32): loss, acc, a fixed sample of the updated trainable parameters")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--clips", type=int, default=0, help="clips per GPU (default: the workload's)")
     ap.add_argument("--train-encoder", action="store_true", help="train_config.freeze_encoder=false (Whisper workloads): the encoder "
@@ -383,6 +458,9 @@ def main():
             fail(args, f"N = {world} ranks over backend '{backend}' with {len(set(idents))} distinct device(s): a scaling line needs backend nccl (= RCCL) "
                        f"and one MI355X per rank (SLAM_DIST_BACKEND / a shared device is only accepted with --functional-gloo)")
 
+    # the counter-based LoRA dropout masks derive from torch.initial_seed(): fixed per rank, so that the same arguments give the same
+    # inputs -- and, the kernels being deterministic, the same outputs -- from run to run
+    torch.manual_seed(rank_seed(rank))
     # recipe defaults (examples/asr_librispeech/asr_config.py:29-37): LoRA on q_proj,v_proj with lora_dropout 0.05 live in
     # train mode ("dropout 0 for parity, 0.05 for throughput"); r per BASELINE.json
     wl = WORKLOADS[args.workload]
@@ -425,12 +503,14 @@ def main():
 
     # warm-up outside the kernel timer, then the timed region (measure(): barrier + synchronize on both sides, MAX over ranks)
     measure(step, 0, args.warmup, world, dist, torch.cuda.synchronize, dev)
-    sampled.update(on=True, i=0, n=0)
+    sampled.update(on=args.full, i=0, n=0)     # (a plain run records no per-launch events)
     if gsync is not None:
         gsync.time_finish = True    # HIP events around finish(): the part of the gradient exchange the backward did not hide
     (loss, acc), elapsed, comm_exposed_ms = measure(step, args.steps, 0, world, dist, torch.cuda.synchronize, dev,
                                                     comm_ms_fn=(gsync.exposed_ms_per_step if gsync is not None else None))
     n_timed = max(1, sampled["n"])           # steps of the timed region that carried per-launch events
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, acc)
     if rank != 0:
         if world > 1:
             dist.barrier()
@@ -448,39 +528,7 @@ def main():
     if rows_skipped and _mm.LAST_LAYER_LABEL_ROWS:
         skipped += 2 * 2 * rows_skipped * (d_ * d_ + 3 * d_ * F_)
     executed_flops = step_flops - skipped * n_clips
-    ksum = timer.summary()
-    gemm_all = [v for k, v in ksum.items() if k.startswith("gemm_nt")]
-    gemm_ms = sum(v["total_ms"] for v in gemm_all)
-    gemm_tf_all = sum(v["work"] for v in gemm_all) / (gemm_ms * 1e-3) / 1e12
-    dom = max((k for k in ksum if k.startswith("gemm_nt")), key=lambda k: ksum[k]["total_ms"])
-    g = ksum[dom]  # the dominant kernel (largest share of the step): one template instance of the bf16 GEMM
-    gemm_tf = g["work"] / (g["total_ms"] * 1e-3) / 1e12
-    kern = {k: dict(launches_per_step=v["launches"] / n_timed, ms_per_step=v["total_ms"] / n_timed,
-                    avg_ms=v["avg_ms"], TFLOPs=v["work"] / (v["total_ms"] * 1e-3) / 1e12,
-                    **({"algorithmic_GB_per_launch": v["bytes"] / v["launches"] / 1e9} if v.get("bytes") else {}))
-            for k, v in ksum.items()}
-    traffic, traffic_src = (traffic_for(dom) if args.workload == "c3" else (None, None))
-    roof = {"bound": "mfma", "kernel": dom + " (slam_gemm_bf16_nt)", "achieved": gemm_tf,
-            "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_BF16_TFLOPS, "traffic": None,
-            "avg_launch_ms": g["avg_ms"], "launches_per_step": g["launches"] / n_timed,
-            "share_of_step": g["total_ms"] / n_timed / ms_per_step,
-            "timing": f"HIP events around every launch on {n_timed} of the {args.steps} timed steps (every {KERNEL_TIMING_EVERY}th, from the first): "
-                      f"~1 170 events per step cost it 0.9 %, so they are not recorded on every step",
-            "algorithmic_bytes_per_launch": g["bytes"] / g["launches"] if g.get("bytes") else None,
-            "all_gemm_instances": {"achieved": gemm_tf_all, "share_of_step": gemm_ms / n_timed / ms_per_step}}
-    pmc = pmc_for(dom) if args.workload == "c3" else None
-    if pmc is not None:
-        # MFMA-busy cycles / (active cycles x 256 CUs x 4 SIMDs) of the dominant kernel, longest-running shape first; at the clock the
-        # chip sustained under that kernel (power-limited: 1.55-1.78 GHz of 2.4), the same kernel's TFLOP/s = mfma_util x 2.5 PF x clock / 2.4
-        big = max(pmc["per_shape"].values(), key=lambda v: v["duration_us"])
-        roof["mfma_util"] = big["mfma_util"]
-        roof["effective_clock_GHz"] = big["effective_clock_GHz"]
-        roof["pmc_detail"] = pmc
-    if traffic is not None:
-        hbm = traffic["fetch_bytes_per_launch"] + traffic["write_bytes_per_launch"]
-        roof["traffic"] = hbm
-        roof["traffic_detail"] = dict(traffic, unit="bytes per launch (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE)", source=traffic_src,
-                                      ratio_to_algorithmic=(hbm / roof["algorithmic_bytes_per_launch"]) if roof["algorithmic_bytes_per_launch"] else None)
+    roof, kern = kernel_figures(timer.summary(), n_timed, args.steps, ms_per_step, args.workload) if args.full else (None, None)
     enc_desc = {"c1": "whisper-tiny -> tinyllama-1.1b, linear projector k=5, LoRA r8",
                 "c3": "whisper-large-v3 -> llama-3-8b, linear projector k=5, LoRA r16",
                 "c2": "whisper-base -> llama-3-8b, linear projector k=5, LoRA r16",
@@ -524,10 +572,9 @@ def main():
         # mfu: the FLOPs the step executed; mfu_model: SURVEY 8(d)'s model (every row through the head) over the same time
         "mfu": executed_flops / (ms_per_step * 1e-3) / (PEAK_BF16_TFLOPS * 1e12),
         "mfu_model": step_flops / (ms_per_step * 1e-3) / (PEAK_BF16_TFLOPS * 1e12),
-        "roofline": roof,
-        "kernels": kern,
+        **({"roofline": roof, "kernels": kern} if args.full else {}),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         del model, opt, batch, step_model
         torch.cuda.empty_cache()
         try:

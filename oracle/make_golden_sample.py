@@ -17,16 +17,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import slam_oracle as O  # noqa: E402
 from oracle.make_golden import GOLD, build_reference  # noqa: E402
 from oracle.make_golden_cases import GENERATE_CASE  # noqa: E402
-
-# (seed 13 of the third run was dropped: one draw sits on an fp32 knife edge between the oracle's full-sequence recompute and HF's
-# KV-cache logits; the tokens split at step 9 of one row)
-RUNS = (  # (num_beams, temperature, top_k, top_p, repetition_penalty, seed)
-    (1, 1.0, 50, 1.0, 1.0, 11), (1, 0.7, 50, 0.9, 1.0, 12), (1, 1.3, 0, 0.8, 1.2, 23),
-    (4, 1.0, 50, 1.0, 1.0, 14), (4, 0.8, 20, 0.95, 1.0, 15), (3, 1.0, 0, 0.9, 1.3, 16))
-
-
-def key(nb, temp, tk, tp, rp, seed):
-    return f"tokens.b{nb}.t{temp}.k{tk}.p{tp}.rp{rp}.seed{seed}"
+from oracle.make_golden_cases import SAMPLE_RUNS as RUNS  # noqa: E402
+from oracle.make_golden_cases import sample_key as key  # noqa: E402
 
 
 def main():

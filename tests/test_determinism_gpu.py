@@ -152,3 +152,29 @@ def test_training_step_is_bit_reproducible_and_reads_no_uninitialised_scratch(de
         bad = _offenders(lambda ctx: _llm_step(dev, ctx, packed), lambda r: r[0] == l1 and r[1] == a1 and torch.equal(r[2], g1))
         raise AssertionError(f"result depends on the content of un-initialised scratch allocated at {bad}: loss {l1} vs {l3}, "
                              f"{int((g1 != g3).sum())} gradient elements differ")
+
+
+def test_bench_dump_outputs_repeat_bit_for_bit(dev, tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same bits (seeded batch, weights and dropout; deterministic
+    kernels), a plain run and a --full run (per-launch HIP events on sampled steps) alike; the figures of --full stay out of a plain line"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c1"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, env=env, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines[name] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["unit"] == "audio-seconds/sec"
+    assert not {"roofline", "kernels", "cpu_baseline"} & set(plain) and full["roofline"]["achieved"] > 0 and full["kernels"]
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == ["acc.npy", "loss.npy", "params_sample.npy"] == sorted(os.listdir(tmp_path / "full"))
+    for f in files:
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), f
+    assert float(np.load(tmp_path / "plain" / "loss.npy")) == plain["loss"]

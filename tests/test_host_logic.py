@@ -107,6 +107,29 @@ def test_flop_model_matches_survey_worked_example():
     assert batcher.frames_for_hbm() > 60000
 
 
+def test_bench_dump_outputs_is_a_fixed_float32_sample(tmp_path):
+    """bench.py --dump-outputs: loss / acc / a parameter sample as float32 .npy, small tensors whole, large ones sampled at indices that
+    depend only on the tensor's name and size (two dumps of the same state are identical), 64 MB at most"""
+    import types
+
+    import bench
+    g = torch.Generator().manual_seed(0)
+    params = {"b.small": torch.randn(100, generator=g), "a.big": torch.randn(300, 1000, generator=g)}
+    model = types.SimpleNamespace(store=types.SimpleNamespace(params=params))
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), model, torch.tensor(1.5), torch.tensor(0.25))
+    files = sorted(os.listdir(tmp_path / "one"))
+    assert files == ["acc.npy", "loss.npy", "params_sample.npy"] == sorted(os.listdir(tmp_path / "two"))
+    one = {f: np.load(tmp_path / "one" / f) for f in files}
+    for f in files:
+        assert one[f].dtype == np.float32 and np.array_equal(one[f], np.load(tmp_path / "two" / f)), f
+    assert float(one["loss.npy"]) == 1.5 and float(one["acc.npy"]) == 0.25
+    s = one["params_sample.npy"]
+    assert s.shape == (bench.DUMP_SAMPLE_PER_TENSOR + 100,)                       # sorted names: a.big sampled, then b.small whole
+    assert np.array_equal(s[-100:], params["b.small"].numpy()) and np.isin(s[:-100], params["a.big"].numpy()).all()
+    assert bench.DUMP_SAMPLE_TOTAL * 4 <= 64 << 20
+
+
 @pytest.mark.parametrize("scale", [24.0, 5.0])
 def test_decode_bookkeeping_matches_reference_generate(scale):
     """the product's beam / greedy bookkeeping (slam_llm_amd/decode.py), driven on CPU by the oracle's fp32 model
@@ -149,7 +172,8 @@ def test_sampling_decode_bookkeeping_matches_reference_generate():
     import torch.nn.functional as F
     from oracle import slam_oracle as O
     from oracle.make_golden_cases import GENERATE_CASE as C
-    from oracle.make_golden_sample import RUNS, key
+    from oracle.make_golden_cases import SAMPLE_RUNS as RUNS
+    from oracle.make_golden_cases import sample_key as key
     from slam_llm_amd import decode
     from tests.test_oracle_golden import generate_case_weights
     fx, fg = G.load("generate_sample"), G.load("generate")

@@ -3,8 +3,7 @@ recipe config defaults, and the two dataset formats.
 
 * loader: `model_config.file = "<path>.py:model_factory"` / `dataset_config.file = "<path>.py:get_speech_dataset"` resolved by
   src/slam_llm/utils/model_utils.py:4-29 / utils/dataset_utils.py:14-57 (split on ":", require a .py file on disk,
-  SourceFileLoader by path, getattr).  When /root/reference is present (authoring container) the reference's OWN loader
-  source is executed (loaded by path: its package __init__ pulls deepspeed); everywhere else a restatement is used.
+  SourceFileLoader by path, getattr), restated line by line below (the reference's own source is not part of this repository).
 * configs: tests/golden/ref_configs.json = the dataclass defaults of examples/asr_librispeech/asr_config.py:8-130 and
   examples/aispeech_asr/aispeech_asr_config.py:7-143 (oracle/make_golden_configs.py), plus the `++a.b=v` overrides the five
   BASELINE.json configs imply.
@@ -15,8 +14,6 @@ import json
 import logging
 import os
 import struct
-import sys
-import types
 from pathlib import Path
 
 import numpy as np
@@ -28,7 +25,6 @@ from tests import golden_util as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLUGIN = os.path.join(ROOT, "slam_llm_amd", "slam_model_hip.py")
-REF_UTILS = "/root/reference/src/slam_llm/utils"
 
 
 class Cfg(dict):
@@ -75,26 +71,7 @@ def _restated_loaders():
 
 def loaders():
     """(get_custom_model_factory, get_custom_dataset, origin)"""
-    if not os.path.isdir(REF_UTILS):
-        return _restated_loaders()
-    spec = importlib.util.spec_from_file_location("ref_dataset_utils", os.path.join(REF_UTILS, "dataset_utils.py"))
-    du = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(du)
-    saved = {k: sys.modules.get(k) for k in ("slam_llm", "slam_llm.utils", "slam_llm.utils.dataset_utils")}
-    try:   # model_utils.py:1 does `from slam_llm.utils.dataset_utils import load_module_from_py_file`
-        sys.modules["slam_llm"] = types.ModuleType("slam_llm")
-        sys.modules["slam_llm.utils"] = types.ModuleType("slam_llm.utils")
-        sys.modules["slam_llm.utils.dataset_utils"] = du
-        spec = importlib.util.spec_from_file_location("ref_model_utils", os.path.join(REF_UTILS, "model_utils.py"))
-        mu = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mu)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return mu.get_custom_model_factory, du.get_custom_dataset, "reference"
+    return _restated_loaders()
 
 
 def ref_defaults(recipe):

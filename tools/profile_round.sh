@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 for wl in c1 c2 c4; do
-  python bench.py --workload $wl --steps 8 --warmup 3 > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "bench $wl failed"
+  python bench.py --workload $wl --steps 8 --warmup 3 --full > $O/bench_$wl.json 2> $O/bench_$wl.err || echo "bench $wl failed"
 done
 (cd /tmp && rocprofv3 --kernel-trace --stats -d $O/prof_c3 -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline > $O/prof_c3.json 2> $O/prof_c3.err)
 python tools/rocpd_stats.py $(ls $O/prof_c3/*/*.db | head -1) $O/r02_c3_kernel_stats.md > /dev/null

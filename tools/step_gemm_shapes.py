@@ -12,7 +12,7 @@ from slam_llm_amd import ops  # noqa: E402
 ops.TIMER_SHAPES = True
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
 import io, contextlib  # noqa: E402
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
