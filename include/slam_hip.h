@@ -394,6 +394,16 @@ int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b, int64_t ld
                      const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R, int64_t beams,
                      int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream);
 
+/* slam_attn_decode with a q|k|v projection bias (Qwen2): qkv_bias [(Hq+2Hkv)*D] fp32, or null (then identical to
+ * slam_attn_decode).  The bias is added in fp32 to the new token's GEMM output and rounded to bf16 (HF's biased Linear),
+ * before the LoRA delta and RoPE.  Hq/Hkv may be any value in [1, 8]. */
+int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                          const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt,
+                          const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen, int32_t* ancestors,
+                          const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R, int64_t beams,
+                          int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,7 @@ void skinny_plan(int64_t N, int64_t K, int64_t splits, int* S, int* kslice) {
 struct DecodeAttnParams {
   const bf16_t* qkv; int64_t ld;   // [R, (Hq+2Hkv)*D (+ lora_r)]: new token's q|k|v (pre-RoPE) (| u = x A^T)
   const bf16_t* lora_b; int64_t ldlb; int lora_r;  // packed (alpha/r) B: [(Hq+2Hkv)*D, >= lora_r] or null
+  const float* bias;               // [(Hq+2Hkv)*D] fp32 q|k|v projection bias (Qwen2) or null
   const float* cosT; const float* sinT; const int* positions;  // RoPE tables [P, D/2], position per row
   const bf16_t* Kp; const bf16_t* Vp;  // prompt KV [B, Tp, Hkv*D]
   const int* start;                // [B] first valid prompt slot (left padding)
@@ -399,6 +400,10 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
       // column of head hh in the fused q|k|v output
       const int col = hh < REP ? (hk * REP + hh) * D : (hh == REP ? QD + hk * D : QD + KD + hk * D);
       float x1 = bf2f(row[col + d]), x2 = bf2f(row[col + D / 2 + d]);
+      if (p.bias) {     // Linear with bias (HF): x W^T + b in fp32, one bf16 rounding, before the LoRA delta and RoPE
+        x1 = bf2f(f2bf(x1 + p.bias[col + d]));
+        x2 = bf2f(f2bf(x2 + p.bias[col + D / 2 + d]));
+      }
       if (p.lora_b) {   // peft: result = base(x) + scale * B(A(x)), both terms rounded to bf16 before the add
         const bf16_t* u = row + QD + 2 * KD;
         const bf16_t* b1 = p.lora_b + (int64_t)(col + d) * p.ldlb;
@@ -529,7 +534,11 @@ int launch_attn_decode(const DecodeAttnParams& p, int rep, int R, hipStream_t st
   switch (rep) {
     case 1: hipLaunchKernelGGL((attn_decode_kernel<D, 1>), grid, dim3(1024), 0, st, p); break;
     case 2: hipLaunchKernelGGL((attn_decode_kernel<D, 2>), grid, dim3(1024), 0, st, p); break;
+    case 3: hipLaunchKernelGGL((attn_decode_kernel<D, 3>), grid, dim3(1024), 0, st, p); break;
     case 4: hipLaunchKernelGGL((attn_decode_kernel<D, 4>), grid, dim3(1024), 0, st, p); break;
+    case 5: hipLaunchKernelGGL((attn_decode_kernel<D, 5>), grid, dim3(1024), 0, st, p); break;
+    case 6: hipLaunchKernelGGL((attn_decode_kernel<D, 6>), grid, dim3(1024), 0, st, p); break;
+    case 7: hipLaunchKernelGGL((attn_decode_kernel<D, 7>), grid, dim3(1024), 0, st, p); break;
     case 8: hipLaunchKernelGGL((attn_decode_kernel<D, 8>), grid, dim3(1024), 0, st, p); break;
     default: return -1;
   }
@@ -593,22 +602,22 @@ extern "C" int slam_gemm_skinny_bf16_nt(const void* A, int64_t lda, const void* 
   return 0;
 }
 
-extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
-                                const float* cos_table, const float* sin_table, const int32_t* positions,
-                                const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
-                                void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O,
-                                int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv,
-                                int64_t D, float scale, void* stream) {
+static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                            const float* qkv_bias, const float* cos_table, const float* sin_table, const int32_t* positions,
+                            const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen,
+                            int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R,
+                            int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream) {
   SLAM_CHECK_ARG(qkv && cos_table && sin_table && positions && k_prompt && v_prompt && k_gen && v_gen && ancestors && O,
-                 "slam_attn_decode: null pointer");
-  SLAM_CHECK_ARG(D == 64 || D == 128, "slam_attn_decode: head_dim must be 64 or 128 (got %lld)", (long long)D);
+                 "%s: null pointer", fn);
+  SLAM_CHECK_ARG(D == 64 || D == 128, "%s: head_dim must be 64 or 128 (got %lld)", fn, (long long)D);
   SLAM_CHECK_ARG(R > 0 && beams > 0 && R % beams == 0 && Tp >= 0 && G > 0 && G <= MAXG,
-                 "slam_attn_decode: bad sizes (generated-token capacity must be <= %d)", MAXG);
-  SLAM_CHECK_ARG(gen_count_dev || (gen_count >= 0 && gen_count < G), "slam_attn_decode: generated-token cache full");
-  SLAM_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "slam_attn_decode: Hq must be a multiple of Hkv");
-  SLAM_CHECK_ARG(!lora_b || (lora_r > 0 && ldlb >= lora_r), "slam_attn_decode: bad LoRA block");
+                 "%s: bad sizes (generated-token capacity must be <= %d)", fn, MAXG);
+  SLAM_CHECK_ARG(gen_count_dev || (gen_count >= 0 && gen_count < G), "%s: generated-token cache full", fn);
+  SLAM_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "%s: Hq must be a multiple of Hkv", fn);
+  SLAM_CHECK_ARG(!lora_b || (lora_r > 0 && ldlb >= lora_r), "%s: bad LoRA block", fn);
   DecodeAttnParams p;
   p.qkv = (const bf16_t*)qkv; p.ld = ld; p.lora_b = (const bf16_t*)lora_b; p.ldlb = ldlb; p.lora_r = (int)lora_r;
+  p.bias = qkv_bias;
   p.cosT = cos_table; p.sinT = sin_table; p.positions = positions;
   p.Kp = (const bf16_t*)k_prompt; p.Vp = (const bf16_t*)v_prompt; p.start = prompt_start;
   p.Kg = (bf16_t*)k_gen; p.Vg = (bf16_t*)v_gen; p.anc = ancestors;
@@ -617,7 +626,29 @@ extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b,
   p.scale_log2 = scale * 1.44269504088896340736f;
   const int rc = D == 64 ? launch_attn_decode<64>(p, (int)(Hq / Hkv), (int)R, (hipStream_t)stream)
                          : launch_attn_decode<128>(p, (int)(Hq / Hkv), (int)R, (hipStream_t)stream);
-  SLAM_CHECK_ARG(rc == 0, "slam_attn_decode: Hq/Hkv must be 1, 2, 4 or 8 (got %lld)", (long long)(Hq / Hkv));
-  SLAM_CHECK_LAUNCH("slam_attn_decode");
+  SLAM_CHECK_ARG(rc == 0, "%s: Hq/Hkv must be in [1, 8] (got %lld)", fn, (long long)(Hq / Hkv));
+  SLAM_CHECK_LAUNCH(fn);
   return 0;
+}
+
+extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                                const float* cos_table, const float* sin_table, const int32_t* positions,
+                                const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
+                                void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O,
+                                int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv,
+                                int64_t D, float scale, void* stream) {
+  return attn_decode_impl("slam_attn_decode", qkv, ld, lora_b, ldlb, lora_r, nullptr, cos_table, sin_table, positions,
+                          k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O, ldo, R,
+                          beams, Tp, G, Hq, Hkv, D, scale, stream);
+}
+
+extern "C" int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                                     const float* cos_table, const float* sin_table, const int32_t* positions,
+                                     const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
+                                     void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count,
+                                     void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
+                                     int64_t Hkv, int64_t D, float scale, const float* qkv_bias, void* stream) {
+  return attn_decode_impl("slam_attn_decode_bias", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, cos_table, sin_table,
+                          positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
+                          ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
 }

@@ -85,6 +85,8 @@ SIGNATURES = {
     "slam_gemm_skinny_bf16_nt": [P, I64, P, I64, P, I64, I64, P, I64, I64, I64, I64, P, I64, I32, I32, P, I64, I64, P],
     "slam_attn_decode": [P, I64, P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, I64,
                          I64, F, P],
+    "slam_attn_decode_bias": [P, I64, P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, I64,
+                              I64, F, P, P],
     "slam_embed_splice_fwd": [P, P, P, I64, P, I64, P, I64, P, I64, I64, I64, I64, P],
     "slam_embed_splice_bwd": [P, P, I64, P, I64, I64, I64, I64, I64, P],
     "slam_ce_targets": [P, P, P, I64, I64, I64, P],

@@ -97,13 +97,28 @@ PRESETS = {
     "vicuna-7b": dict(llm_dim=4096, llm_layers=32, llm_heads=32, llm_kv_heads=32, llm_head_dim=128, llm_ffn=11008,
                       vocab=32000, rope_theta=10000.0, rms_eps=1e-5),
 }
+# Qwen2 / Qwen2.5 (HF Qwen2ForCausalLM config.json of each checkpoint): Llama layout plus a bias on q/k/v_proj, and the lm_head tied
+# to the input embedding up to 3B
+_QWEN2 = dict(rope_theta=1000000.0, rms_eps=1e-6, llm_qkv_bias=True)
+_QWEN2_05B = dict(_QWEN2, llm_dim=896, llm_layers=24, llm_heads=14, llm_kv_heads=2, llm_head_dim=64, llm_ffn=4864, vocab=151936,
+                  tie_embeddings=True)
+_QWEN2_15B = dict(_QWEN2, llm_dim=1536, llm_layers=28, llm_heads=12, llm_kv_heads=2, llm_head_dim=128, llm_ffn=8960, vocab=151936,
+                  tie_embeddings=True)
+_QWEN2_7B = dict(_QWEN2, llm_dim=3584, llm_layers=28, llm_heads=28, llm_kv_heads=4, llm_head_dim=128, llm_ffn=18944, vocab=152064,
+                 tie_embeddings=False)
+PRESETS.update({
+    "qwen2-0.5b": _QWEN2_05B, "qwen2-1.5b": _QWEN2_15B, "qwen2-7b": _QWEN2_7B,
+    "qwen2.5-0.5b": _QWEN2_05B, "qwen2.5-1.5b": _QWEN2_15B, "qwen2.5-7b": _QWEN2_7B,
+    "qwen2.5-3b": dict(_QWEN2, llm_dim=2048, llm_layers=36, llm_heads=16, llm_kv_heads=2, llm_head_dim=128, llm_ffn=11008,
+                       vocab=151936, tie_embeddings=True),
+})
 
 
 def make_config(encoder: Optional[str] = None, llm: Optional[str] = None, **kw) -> dict:
     cfg = dict(n_mels=80, enc_dim=128, enc_heads=2, enc_layers=2, enc_ctx=1500, ds_rate=5, proj_hidden=2048,
                llm_dim=128, llm_layers=2, llm_heads=2, llm_kv_heads=1, llm_head_dim=64, llm_ffn=256, vocab=512,
-               rope_theta=10000.0, rms_eps=1e-5, lora_r=8, lora_alpha=32, lora_targets=("q_proj", "v_proj"),
-               lora_dropout=0.0)
+               rope_theta=10000.0, rms_eps=1e-5, llm_qkv_bias=False, tie_embeddings=False, lora_r=8, lora_alpha=32,
+               lora_targets=("q_proj", "v_proj"), lora_dropout=0.0)
     if encoder:
         cfg.update(PRESETS[encoder])
     if llm:
@@ -2100,7 +2115,9 @@ def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
 
 class HipLlamaLora(nn.Module):
     """Frozen Llama decoder + peft-style LoRA adapters (HF LlamaForCausalLM under peft's LoraModel as built at
-    src/slam_llm/models/slam_model.py:118-221); parameter names follow peft 0.6.0."""
+    src/slam_llm/models/slam_model.py:118-221); parameter names follow peft 0.6.0.  Qwen2 (HF Qwen2ForCausalLM) is the same
+    graph with cfg['llm_qkv_bias'] (a frozen bias on q/k/v_proj, added in the GEMM epilogue / the decode attention prologue) and
+    cfg['tie_embeddings'] (lm_head IS the input embedding)."""
 
     ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
 
@@ -2117,12 +2134,14 @@ class HipLlamaLora(nn.Module):
         self.label_rows_cap = None
         self.last_label_count = None
         self.layers = []
+        self.qkv_bias = bool(cfg.get("llm_qkv_bias", False))
+        self.tied = bool(cfg.get("tie_embeddings", False))
         targets = tuple(cfg.get("lora_targets") or ())
         r, alpha = cfg["lora_r"], cfg["lora_alpha"]
         P = prefix + "base_model.model."
         # reserve in backward-production order: last layer first
         for i in reversed(range(cfg["llm_layers"])):
-            L = SimpleNamespace()
+            L = SimpleNamespace(bias=None)     # bias: fp32 [(Hq + 2 Hkv) D] q|k|v bias (Qwen2) or None
             L.qkv = FusedLinear(d, [("q_proj", Hq * D), ("k_proj", Hkv * D), ("v_proj", Hkv * D)], device)
             L.o = FusedLinear(Hq * D, [("o_proj", d)], device)
             L.gu = FusedLinear(d, [("gate_proj", Fd), ("up_proj", Fd)], device)
@@ -2159,9 +2178,18 @@ class HipLlamaLora(nn.Module):
                     mod = "self_attn." if n in self.ATTN else "mlp."
                     fl.set_base(n, bf(W[p + mod + n + ".weight"]))
                 fl.finalize()
+            if self.qkv_bias:
+                L.bias = torch.cat([f32(W[p + "self_attn." + n + ".bias"]) for n, _ in L.qkv.parts]).contiguous()
             L.ln1, L.ln2 = f32(W[p + "input_layernorm.weight"]), f32(W[p + "post_attention_layernorm.weight"])
         self.norm_w = f32(W[P + "model.norm.weight"])
-        self.lm_head = bf(W[P + "lm_head.weight"]).contiguous()
+        if self.tied:
+            # tie_word_embeddings: HF checkpoints carry no lm_head.weight; one that does must hold the embedding itself
+            head = W.get(P + "lm_head.weight")
+            if head is not None and not torch.equal(bf(head), self.embed):
+                raise ValueError("tie_embeddings: the state dict's lm_head.weight differs from model.embed_tokens.weight")
+            self.lm_head = self.embed
+        else:
+            self.lm_head = bf(W[P + "lm_head.weight"]).contiguous()
         self.lm_headT = ops.transpose(self.lm_head, Rp=self.lm_head.shape[0])
         return self
 
@@ -2170,7 +2198,8 @@ class HipLlamaLora(nn.Module):
         d, Fd, V = cfg["llm_dim"], cfg["llm_ffn"], cfg["vocab"]
         g = torch.Generator(device=dev).manual_seed(seed)
         rn = lambda *s, std=0.02: (torch.randn(*s, generator=g, device=dev) * std)  # noqa: E731
-        self.embed = rn(V, d, std=1.0).to(torch.bfloat16)
+        # a tied head reads the embedding as its weight: the head's scale then, so that the logits stay O(1)
+        self.embed = rn(V, d, std=d ** -0.5 if self.tied else 1.0).to(torch.bfloat16)
         for L in self.layers:
             for fl in (L.qkv, L.o, L.gu, L.down):
                 for n, rows in fl.parts:
@@ -2178,8 +2207,14 @@ class HipLlamaLora(nn.Module):
                 fl.finalize()
             L.ln1, L.ln2 = 1 + rn(d, std=0.1), 1 + rn(d, std=0.1)
         self.norm_w = 1 + rn(d, std=0.1)
-        self.lm_head = rn(V, d, std=d ** -0.5).to(torch.bfloat16)
+        if self.tied:
+            self.lm_head = self.embed
+        else:
+            self.lm_head = rn(V, d, std=d ** -0.5).to(torch.bfloat16)
         self.lm_headT = ops.transpose(self.lm_head, Rp=V)
+        if self.qkv_bias:   # drawn last: the draws of a bias-free config stay exactly as they were
+            for L in self.layers:
+                L.bias = rn(L.qkv.N, std=0.5).to(torch.bfloat16).float()
         return self
 
     def refresh(self):
@@ -2242,7 +2277,7 @@ class HipLlamaLora(nn.Module):
             x1 = L.qkv.new_input(M, for_forward=True)
             _, rstd1 = ops.rmsnorm_fwd(h, L.ln1, eps, out=x1[:, :d])
             dq_, do_, dg_, dd_ = drop_for(L.qkv), drop_for(L.o), drop_for(L.gu), drop_for(L.down)
-            qkv = L.qkv.forward(x1, st, drop=dq_)
+            qkv = L.qkv.forward(x1, st, bias=L.bias, drop=dq_)
             ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)     # q and k heads: adjacent columns, one launch
             o_ext = L.o.new_input(M)
             _, lse = ops.attn_fwd(qkv[:, : Hq * D], qkv[:, Hq * D: (Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:], B, T, Hq, Hkv, D, True, scale,
@@ -2358,7 +2393,7 @@ class HipLlamaLora(nn.Module):
         for li, L in enumerate(self.layers):
             x1 = L.qkv.new_input(M)
             ops.rmsnorm_fwd(h, L.ln1, eps, out=x1[:, :d])
-            qkv = L.qkv.forward(x1, st)
+            qkv = L.qkv.forward(x1, st, bias=L.bias)
             ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)
             cache.Kp[li].copy_(qkv[:, Hq * D:(Hq + Hkv) * D].view(B, T, Hkv * D))
             cache.Vp[li].copy_(qkv[:, (Hq + Hkv) * D:].view(B, T, Hkv * D))
@@ -2378,8 +2413,8 @@ class HipLlamaLora(nn.Module):
     def _decode_body(self, cache) -> torch.Tensor:
         """one decode step over static buffers (cache.tok, cache.next_pos, cache.n_dev, cache.anc): every launch
         reads the step index from device memory, so the sequence can be captured once in a HIP graph and replayed.
-        7 launches per layer for <= 64 hypotheses: rmsnorm, qkv (+ LoRA A rows), attention (LoRA delta + RoPE + KV
-        append fused), o_proj (+ residual), rmsnorm, gate_up (+ SwiGLU), down_proj (+ residual)."""
+        7 launches per layer for <= 64 hypotheses: rmsnorm, qkv (+ LoRA A rows), attention (q|k|v bias + LoRA delta + RoPE + KV
+        append fused; the q|k|v GEMM itself never adds the bias), o_proj (+ residual), rmsnorm, gate_up (+ SwiGLU), down_proj (+ residual)."""
         cfg, st = self.cfg, self.store
         d, Hq, Hkv, D, Fd = cfg["llm_dim"], cfg["llm_heads"], cfg["llm_kv_heads"], cfg["llm_head_dim"], cfg["llm_ffn"]
         R, eps = cache.R, cfg["rms_eps"]
@@ -2402,7 +2437,7 @@ class HipLlamaLora(nn.Module):
             o_ext = L.o.new_input(R)
             ops.attn_decode(qkv, lora_b, lora_r, cos, sin, cache.next_pos, cache.Kp[li], cache.Vp[li], cache.start,
                             cache.Kg[li], cache.Vg[li], cache.anc, cache.n_dev, cache.n, cache.beams, Hq, Hkv, D,
-                            D ** -0.5, o_ext)
+                            D ** -0.5, o_ext, qkv_bias=L.bias)
             h_mid = L.o.forward(o_ext, st, residual=h)
             x2 = L.gu.new_input(R)
             ops.rmsnorm_fwd(h_mid, L.ln2, eps, out=x2[:, :d])
@@ -2750,6 +2785,7 @@ class SlamHipModel(nn.Module):
             self.encoder.refold_query_bias()
         for L in self.llm.layers:
             rnd(L.ln1); rnd(L.ln2)
+            rnd(L.bias)     # Qwen2 q|k|v bias: the reference rounds the bias itself; the kernels read the rounded value in fp32
         rnd(self.llm.norm_w)
 
     # ---- forward -------------------------------------------------------------------------------------

@@ -673,16 +673,21 @@ def attn_bwd(q2d, k2d, v2d, o2d, do2d, lse, dq2d, dk2d, dv2d, B, T, Hq, Hkv, D, 
 
 
 def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors,
-                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out):
-    """one decode step of attention per hypothesis: LoRA delta + RoPE + KV append of the new token, then one query per
-    row against [prompt KV of its batch item | generated KV via the ancestor table]."""
+                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None):
+    """one decode step of attention per hypothesis: (q|k|v bias +) LoRA delta + RoPE + KV append of the new token, then one
+    query per row against [prompt KV of its batch item | generated KV via the ancestor table].  qkv_bias: fp32
+    [(Hq + 2 Hkv) D] (Qwen2) or None."""
     R, G = k_gen.shape[0], k_gen.shape[1]
     Tp = k_prompt.shape[1]
-    _timed("attn_decode", 4.0 * R * Hkv * D * (Tp + gen_count + 1),
-           lambda: call("slam_attn_decode", _p(qkv), _ld(qkv), _p(lora_b), _ld(lora_b) if lora_b is not None else 0, lora_r,
-                        _p(cos), _p(sin), _p(positions), _p(k_prompt), _p(v_prompt), _p(prompt_start), _p(k_gen), _p(v_gen),
-                        _p(ancestors), _p(gen_count_dev), gen_count, _p(out), _ld(out), R, beams, Tp, G, Hq, Hkv, D, scale,
-                        _s()))
+    args = (_p(qkv), _ld(qkv), _p(lora_b), _ld(lora_b) if lora_b is not None else 0, lora_r, _p(cos), _p(sin), _p(positions),
+            _p(k_prompt), _p(v_prompt), _p(prompt_start), _p(k_gen), _p(v_gen), _p(ancestors), _p(gen_count_dev), gen_count,
+            _p(out), _ld(out), R, beams, Tp, G, Hq, Hkv, D, scale)
+    if qkv_bias is None:
+        fn = lambda: call("slam_attn_decode", *args, _s())  # noqa: E731
+    else:
+        assert qkv_bias.dtype == torch.float32 and qkv_bias.is_contiguous() and qkv_bias.numel() == (Hq + 2 * Hkv) * D
+        fn = lambda: call("slam_attn_decode_bias", *args, _p(qkv_bias), _s())  # noqa: E731
+    _timed("attn_decode", 4.0 * R * Hkv * D * (Tp + gen_count + 1), fn)
     return out
 
 

@@ -39,6 +39,17 @@ def _get(cfg, key, default=None):
 PRESET_ALIASES = {"xtralarge": "xlarge", "extralarge": "xlarge", "x-large": "xlarge", "xtra-large": "xlarge"}
 
 
+def _name_has(n: str, k: str) -> bool:
+    """k occurs in n, and not as the tail of a longer version number: `qwen2-7b` is no match for `qwen2.5-7b` (nor the reverse,
+    as neither string contains the other), and `qwen2.5-0.5b` none for `qwen2.5-10.5b`"""
+    i = n.find(k)
+    while i >= 0:
+        if i == 0 or not (n[i - 1].isdigit() or n[i - 1] == "."):
+            return True
+        i = n.find(k, i + 1)
+    return False
+
+
 def _guess_preset(name: str, table) -> str:
     """architecture preset from a checkpoint name.  The BASENAME votes first (a directory such as `/hubert-large-models/` must not
     pick the geometry of `hubert_base_ls960.pt` inside it); the reference recipes' spellings are normalised first
@@ -51,7 +62,7 @@ def _guess_preset(name: str, table) -> str:
         for a, b in PRESET_ALIASES.items():
             n = n.replace(a, b)
         for k in sorted(table, key=len, reverse=True):
-            if k in n or k.replace("-", "") in n.replace("-", ""):
+            if _name_has(n, k) or _name_has(n.replace("-", ""), k.replace("-", "")):
                 return k
     raise ValueError(f"cannot map '{name}' to a known architecture preset {sorted(table)}; pass model_config.arch_encoder / arch_llm explicitly")
 
@@ -80,6 +91,73 @@ WAVLM_PRESETS = {
 WAVLM_PRESETS["wavlm-base-plus"] = WAVLM_PRESETS["wavlm-base"]
 
 
+# ---------------------------------------------------------------------------------------------- Hugging Face LLM directories
+HF_LLM_TYPES = ("llama", "qwen2")
+
+
+def hf_llm_geometry(hf_cfg: dict) -> dict:
+    """make_config keys of the decoder an HF `config.json` (LlamaForCausalLM / Qwen2ForCausalLM) describes"""
+    mt = hf_cfg.get("model_type")
+    if mt not in HF_LLM_TYPES:
+        raise NotImplementedError(f"llm_path config.json: model_type {mt!r} is not implemented (the HIP LLM covers {list(HF_LLM_TYPES)})")
+    if mt == "llama" and (hf_cfg.get("attention_bias") or hf_cfg.get("mlp_bias")):
+        raise NotImplementedError("llm_path config.json: Llama with attention_bias / mlp_bias is not implemented")
+    if hf_cfg.get("use_sliding_window"):
+        raise NotImplementedError("llm_path config.json: sliding-window attention (use_sliding_window=true) is not implemented")
+    rope = hf_cfg.get("rope_parameters") or {}
+    scaling = hf_cfg.get("rope_scaling") or {}
+    if scaling.get("rope_type", scaling.get("type", "default")) != "default" or rope.get("rope_type", "default") != "default":
+        raise NotImplementedError("llm_path config.json: scaled RoPE (rope_scaling) is not implemented")
+    theta = hf_cfg.get("rope_theta", rope.get("rope_theta", 10000.0))
+    d, Hq = int(hf_cfg["hidden_size"]), int(hf_cfg["num_attention_heads"])
+    return dict(llm_dim=d, llm_layers=int(hf_cfg["num_hidden_layers"]), llm_heads=Hq,
+                llm_kv_heads=int(hf_cfg.get("num_key_value_heads") or Hq), llm_head_dim=int(hf_cfg.get("head_dim") or d // Hq),
+                llm_ffn=int(hf_cfg["intermediate_size"]), vocab=int(hf_cfg["vocab_size"]), rope_theta=float(theta),
+                rms_eps=float(hf_cfg.get("rms_norm_eps", 1e-6)), llm_qkv_bias=mt == "qwen2",
+                tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)))
+
+
+def read_hf_llm_config(llm_path):
+    """geometry from `<llm_path>/config.json` when llm_path is an HF model directory, else None"""
+    import json
+    if not llm_path or not os.path.isdir(str(llm_path)):
+        return None
+    path = os.path.join(str(llm_path), "config.json")
+    if not os.path.isfile(path):
+        return None
+    with open(path) as f:
+        return hf_llm_geometry(json.load(f))
+
+
+def hf_to_reference_names(sd: dict, prefix: str = "llm.base_model.model.") -> dict:
+    """HF CausalLM state dict (`model.layers.N...`, `model.embed_tokens.weight`, `lm_head.weight`) -> the reference's names
+    (the LLM under peft at `slam_model.llm`); buffers such as rotary `inv_freq` are dropped.  A tied checkpoint has no
+    lm_head.weight and needs none."""
+    return {prefix + k: v for k, v in sd.items() if (k.startswith("model.") or k == "lm_head.weight") and not k.endswith(".inv_freq")}
+
+
+def load_hf_llm_state(llm_path: str) -> dict:
+    """`model.safetensors`, or the shards `model.safetensors.index.json` names, of an HF model directory, in the reference's names"""
+    import json
+    try:
+        from safetensors.torch import load_file
+    except ImportError as e:
+        raise ImportError("loading an HF model directory (model_config.llm_path) needs the `safetensors` package; install it or pass "
+                          "model_config.llm_state (a state dict in the reference's key names)") from e
+    single, index = os.path.join(llm_path, "model.safetensors"), os.path.join(llm_path, "model.safetensors.index.json")
+    if os.path.isfile(single):
+        files = [single]
+    elif os.path.isfile(index):
+        with open(index) as f:
+            files = [os.path.join(llm_path, n) for n in sorted(set(json.load(f)["weight_map"].values()))]
+    else:
+        raise FileNotFoundError(f"llm_path {llm_path}: neither model.safetensors nor model.safetensors.index.json")
+    sd = {}
+    for fn in files:
+        sd.update(load_file(fn))
+    return hf_to_reference_names(sd)
+
+
 def build_config(train_config, model_config) -> dict:
     enc_name = _get(model_config, "encoder_name", None)
     if enc_name not in ("whisper", "hubert", "wavlm"):
@@ -93,7 +171,12 @@ def build_config(train_config, model_config) -> dict:
                                   "(EncoderProjectorCov1d) or `q-former` (EncoderProjectorQFormer)")
     enc_presets = {k: v for k, v in PRESETS.items() if k.startswith("whisper")}
     llm_presets = {k: v for k, v in PRESETS.items() if not k.startswith("whisper")}
-    llm = _get(model_config, "arch_llm") or _guess_preset(str(_get(model_config, "llm_name", "")), llm_presets)
+    # LLM geometry: an explicit arch_llm preset, else the config.json of an HF llm_path directory, else the preset llm_name names
+    # (arch_overrides, below, wins over all three)
+    llm = _get(model_config, "arch_llm")
+    hf_geom = None if llm else read_hf_llm_config(_get(model_config, "llm_path", None))
+    if not llm and hf_geom is None:
+        llm = _guess_preset(str(_get(model_config, "llm_name", "")), llm_presets)
     peft = _get(train_config, "peft_config", None)
     use_peft = bool(_get(train_config, "use_peft", False))
     # ++model_config.pad_or_trim=false: per-clip mel (aispeech recipes); ++model_config.varlen=true: right-padded batches run
@@ -138,6 +221,8 @@ def build_config(train_config, model_config) -> dict:
                       lora_r=int(_get(peft, "r", 8)), lora_alpha=float(_get(peft, "lora_alpha", 32)),
                       lora_targets=tuple(_get(peft, "target_modules", ("q_proj", "v_proj"))) if use_peft else (),
                       lora_dropout=float(_get(peft, "lora_dropout", 0.05)) if use_peft else 0.0, **extra)
+    if hf_geom is not None:
+        cfg.update(hf_geom)
     overrides = _get(model_config, "arch_overrides", None)   # ++model_config.arch_overrides={llm_layers: 2, ...}: non-preset geometries
     if overrides:
         cfg.update({k: (tuple(v) if isinstance(v, list) else v) for k, v in dict(overrides).items()})
@@ -275,6 +360,9 @@ def model_factory(train_config, model_config, **kwargs):
         model.init_random(seed)
     else:
         W = {}
+        llm_path = _get(model_config, "llm_path", None)
+        if not _get(model_config, "llm_state", None) and llm_path and os.path.isdir(str(llm_path)):
+            W.update(load_hf_llm_state(str(llm_path)))
         for key in ("encoder_state", "llm_state"):
             p = _get(model_config, key, None)
             if p:
