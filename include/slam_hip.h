@@ -404,6 +404,33 @@ int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lora_b, int64
                           int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
                           void* stream);
 
+/* slam_attn_decode_bias with the per-head RMSNorm of Qwen3 (HF Qwen3Attention.forward: q_norm / k_norm over head_dim behind
+ * q_proj / k_proj, before apply_rotary_pos_emb; Qwen3RMSNorm.forward: x * rsqrt(mean(x^2) + eps) in fp32, cast to bf16, times
+ * the weight).  q_norm_w / k_norm_w: [D] fp32, both set or both null (null = slam_attn_decode_bias, bit-identical).  Order on
+ * the new token: bias -> LoRA delta -> per-head RMSNorm -> RoPE -> KV append (HF under peft). */
+int slam_attn_decode_qknorm(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                            const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt,
+                            const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen, int32_t* ancestors,
+                            const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R, int64_t beams,
+                            int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
+                            const float* q_norm_w, const float* k_norm_w, float eps, void* stream);
+
+/* Per-head RMSNorm + RoPE, in place on the Hq + Hkv adjacent heads at columns [col0, col0 + (Hq+Hkv)*D) of qkv [B*T, ld] bf16
+ * (HF Qwen3Attention.forward: q_norm / k_norm then apply_rotary_pos_emb; Qwen3RMSNorm.forward for the two roundings).  Heads
+ * < Hq take q_weight, the others k_weight ([D] fp32).  positions: [B*T] int32 row of the cos/sin tables ([P, D/2] fp32), or null
+ * for position = t.  Training outputs, both set or both null: rstd_out [B*T, Hq+Hkv] fp32 and x_out [B*T, (Hq+Hkv)*D] bf16, a
+ * copy of the pre-norm columns.  D in {64, 128}. */
+int slam_head_rmsnorm_rope(void* qkv, int64_t ld, int64_t col0, const float* q_weight, const float* k_weight, float eps,
+                           const float* cos_table, const float* sin_table, const int32_t* positions, float* rstd_out,
+                           void* x_out, int64_t B, int64_t T, int64_t Hq, int64_t Hkv, int64_t D, void* stream);
+
+/* Backward of the per-head RMSNorm (Qwen3RMSNorm.forward) alone, in place on the same columns of dqkv [M, ld] bf16, which hold
+ * dL/d(post-norm, pre-RoPE) as slam_attn_bwd leaves them with its fused RoPE backward: dx = rstd * (g - xhat * mean_D(g * xhat)),
+ * g = w * dy, xhat = x * rstd, in fp32.  x [M, (Hq+Hkv)*D] bf16 and rstd [M, Hq+Hkv] fp32 are slam_head_rmsnorm_rope's training
+ * outputs.  No weight gradient (frozen LLM); columns outside the q|k heads are not touched. */
+int slam_head_rmsnorm_bwd(void* dqkv, int64_t ld, int64_t col0, const void* x, const float* rstd, const float* q_weight,
+                          const float* k_weight, int64_t M, int64_t Hq, int64_t Hkv, int64_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,7 @@ struct DecodeAttnParams {
   const bf16_t* qkv; int64_t ld;   // [R, (Hq+2Hkv)*D (+ lora_r)]: new token's q|k|v (pre-RoPE) (| u = x A^T)
   const bf16_t* lora_b; int64_t ldlb; int lora_r;  // packed (alpha/r) B: [(Hq+2Hkv)*D, >= lora_r] or null
   const float* bias;               // [(Hq+2Hkv)*D] fp32 q|k|v projection bias (Qwen2) or null
+  const float* qnorm; const float* knorm; float norm_eps;  // [D] fp32 per-head RMSNorm weights of q and k (Qwen3) or null
   const float* cosT; const float* sinT; const int* positions;  // RoPE tables [P, D/2], position per row
   const bf16_t* Kp; const bf16_t* Vp;  // prompt KV [B, Tp, Hkv*D]
   const int* start;                // [B] first valid prompt slot (left padding)
@@ -430,6 +431,18 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
         x1 = bf2f(f2bf(x1 + bf2f(f2bf(d1))));
         x2 = bf2f(f2bf(x2 + bf2f(f2bf(d2))));
       }
+      if (p.qnorm && hh <= REP) {
+        // Qwen3: RMSNorm over the head (q_norm / k_norm) behind the projection, bias and LoRA delta, before RoPE.  The D/2 threads
+        // of head hh are consecutive lanes (a whole wave at D = 128, an aligned half wave at D = 64; NH * D/2 <= 1024 threads, so
+        // every (head, d) pair is met in this one pass) and leave the loop together: the sum stays inside those lanes.
+        float ss = x1 * x1 + x2 * x2;
+#pragma unroll
+        for (int o = D / 4; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+        const float rstd = rsqrtf(ss / (float)D + p.norm_eps);
+        const float* w = hh < REP ? p.qnorm : p.knorm;
+        x1 = bf2f(f2bf(w[d] * bf2f(f2bf(x1 * rstd))));   // Qwen3RMSNorm: cast back to bf16, then the weight
+        x2 = bf2f(f2bf(w[D / 2 + d] * bf2f(f2bf(x2 * rstd))));
+      }
       if (hh <= REP) {  // q heads and k: rotate (HF rotate_half convention), round to bf16 like the prefill path
         const float cs = p.cosT[(int64_t)pos * (D / 2) + d], sn = p.sinT[(int64_t)pos * (D / 2) + d];
         const float y1 = bf2f(f2bf(x1 * cs - x2 * sn)), y2 = bf2f(f2bf(x2 * cs + x1 * sn));
@@ -603,8 +616,8 @@ extern "C" int slam_gemm_skinny_bf16_nt(const void* A, int64_t lda, const void* 
 }
 
 static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
-                            const float* qkv_bias, const float* cos_table, const float* sin_table, const int32_t* positions,
-                            const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen,
+                            const float* qkv_bias, const float* q_norm_w, const float* k_norm_w, float norm_eps,
+                            const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen,
                             int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R,
                             int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream) {
   SLAM_CHECK_ARG(qkv && cos_table && sin_table && positions && k_prompt && v_prompt && k_gen && v_gen && ancestors && O,
@@ -615,9 +628,11 @@ static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const v
   SLAM_CHECK_ARG(gen_count_dev || (gen_count >= 0 && gen_count < G), "%s: generated-token cache full", fn);
   SLAM_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "%s: Hq must be a multiple of Hkv", fn);
   SLAM_CHECK_ARG(!lora_b || (lora_r > 0 && ldlb >= lora_r), "%s: bad LoRA block", fn);
+  SLAM_CHECK_ARG((q_norm_w == nullptr) == (k_norm_w == nullptr), "%s: q/k norm weights must both be set or both null", fn);
   DecodeAttnParams p;
   p.qkv = (const bf16_t*)qkv; p.ld = ld; p.lora_b = (const bf16_t*)lora_b; p.ldlb = ldlb; p.lora_r = (int)lora_r;
   p.bias = qkv_bias;
+  p.qnorm = q_norm_w; p.knorm = k_norm_w; p.norm_eps = norm_eps;
   p.cosT = cos_table; p.sinT = sin_table; p.positions = positions;
   p.Kp = (const bf16_t*)k_prompt; p.Vp = (const bf16_t*)v_prompt; p.start = prompt_start;
   p.Kg = (bf16_t*)k_gen; p.Vg = (bf16_t*)v_gen; p.anc = ancestors;
@@ -637,7 +652,7 @@ extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b,
                                 void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O,
                                 int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv,
                                 int64_t D, float scale, void* stream) {
-  return attn_decode_impl("slam_attn_decode", qkv, ld, lora_b, ldlb, lora_r, nullptr, cos_table, sin_table, positions,
+  return attn_decode_impl("slam_attn_decode", qkv, ld, lora_b, ldlb, lora_r, nullptr, nullptr, nullptr, 0.f, cos_table, sin_table, positions,
                           k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O, ldo, R,
                           beams, Tp, G, Hq, Hkv, D, scale, stream);
 }
@@ -648,7 +663,20 @@ extern "C" int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lo
                                      void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count,
                                      void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
                                      int64_t Hkv, int64_t D, float scale, const float* qkv_bias, void* stream) {
-  return attn_decode_impl("slam_attn_decode_bias", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, cos_table, sin_table,
-                          positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
+  return attn_decode_impl("slam_attn_decode_bias", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, nullptr, nullptr, 0.f, cos_table,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
                           ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
+}
+
+/* slam_attn_decode_bias plus the per-head RMSNorm of q and k (HF Qwen3Attention.forward: q_norm / k_norm, Qwen3RMSNorm.forward). */
+extern "C" int slam_attn_decode_qknorm(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                                       const float* cos_table, const float* sin_table, const int32_t* positions,
+                                       const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
+                                       void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count,
+                                       void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
+                                       int64_t Hkv, int64_t D, float scale, const float* qkv_bias, const float* q_norm_w,
+                                       const float* k_norm_w, float eps, void* stream) {
+  return attn_decode_impl("slam_attn_decode_qknorm", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count,
+                          O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
 }

@@ -1,4 +1,4 @@
-// HBM-bound row normalisations: LayerNorm (Whisper encoder) and RMSNorm fwd/bwd (Llama).
+// HBM-bound row normalisations: LayerNorm (Whisper encoder), RMSNorm fwd/bwd (Llama) and the per-head q/k RMSNorm (+ RoPE) of Qwen3.
 //
 // Reference semantics:
 //  * openai-whisper LayerNorm computes in fp32 and casts back (called from
@@ -402,7 +402,195 @@ __global__ __launch_bounds__(256) void layernorm_bwd_params_kernel(const bf16_t*
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Per-head RMSNorm of the q and k heads (Qwen3: HF Qwen3Attention.forward applies q_norm / k_norm, a Qwen3RMSNorm over
+// head_dim, to every head after the projection and before apply_rotary_pos_emb), fused with the rotary embedding.
+// A head is D bf16 = D/8 16-byte chunks; RoPE pairs element d with d + D/2, so a lane owns chunk c of the first half AND
+// chunk c of the second half (16 elements) and HC = D/16 neighbouring lanes (4 or 8) own one head: the sum of squares is
+// a DPP reduction inside those lanes, no LDS.  Lanes run over (row, head, c) flat, so a wave reads 64/HC adjacent heads
+// = 2 KB of one row in full lines.
+// ------------------------------------------------------------------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// sum over the HC (4 or 8) consecutive lanes that own one head, result in every one of them
+template <int HC>
+__device__ __forceinline__ float head_sum(float v) {
+  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
+  if constexpr (HC == 8) v += dpp_mov<0x141>(v);  // row_half_mirror: the other quad of the 8
+  return v;
+}
+__device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+}
+
+// in place on columns [col0, col0 + (Hq + Hkv) * D) of qkv: y = rope(w * bf16(x * rstd)), the two roundings of
+// Qwen3RMSNorm.forward (cast back to the input dtype, then the weight) and the rounding of the RoPE kernel above it.
+// rstd_out [M, H] fp32 and x_out [M, H*D] bf16 (the pre-norm values, for the backward) are written when non-null.
+template <int D>
+__global__ __launch_bounds__(256) void head_rmsnorm_rope_kernel(
+    bf16_t* __restrict__ qkv, int64_t ld, int col0, const float* __restrict__ wq, const float* __restrict__ wk, float eps,
+    const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ positions,
+    float* __restrict__ rstd_out, bf16_t* __restrict__ x_out, int64_t M, int T, int Hq, int H) {
+  constexpr int HC = D / 16;
+  const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool ok = item < M * H * HC;      // whole heads are in or out: M * H * HC is a multiple of HC
+  const int c = (int)(item % HC);
+  const int64_t rh = ok ? item / HC : 0;
+  const int h = (int)(rh % H);
+  const int64_t row = rh / H;
+  bf16_t* p = qkv + row * ld + col0 + h * D;
+  u16x8_t x1 = {0, 0, 0, 0, 0, 0, 0, 0}, x2 = x1;
+  if (ok) {
+    x1 = *reinterpret_cast<const u16x8_t*>(p + c * 8);
+    x2 = *reinterpret_cast<const u16x8_t*>(p + D / 2 + c * 8);
+  }
+  float q = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const float a = bf2f(x1[e]), b = bf2f(x2[e]);
+    q += a * a;
+    q += b * b;
+  }
+  const float rstd = rsqrtf(head_sum<HC>(q) / (float)D + eps);
+  if (!ok) return;
+  if (x_out) {
+    bf16_t* xo = x_out + (row * H + h) * D;
+    *reinterpret_cast<u16x8_t*>(xo + c * 8) = x1;
+    *reinterpret_cast<u16x8_t*>(xo + D / 2 + c * 8) = x2;
+  }
+  if (rstd_out && c == 0) rstd_out[row * H + h] = rstd;
+  const float* w = h < Hq ? wq : wk;
+  float w1[8], w2[8], cs8[8], sn8[8];
+  load8f(w + c * 8, w1);
+  load8f(w + D / 2 + c * 8, w2);
+  const int pp = positions ? positions[row] : (int)(row % T);
+  load8f(cosT + (int64_t)pp * (D / 2) + c * 8, cs8);
+  load8f(sinT + (int64_t)pp * (D / 2) + c * 8, sn8);
+  float r1[8], r2[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const float a = bf2f(f2bf(w1[e] * bf2f(f2bf(bf2f(x1[e]) * rstd))));
+    const float bb = bf2f(f2bf(w2[e] * bf2f(f2bf(bf2f(x2[e]) * rstd))));
+    const float cs = cs8[e], sn = sn8[e];
+    r1[e] = a * cs - bb * sn;
+    r2[e] = bb * cs + a * sn;
+  }
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+  u32x4_t o1, o2;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    o1[e] = pack2bf(r1[2 * e], r1[2 * e + 1]);
+    o2[e] = pack2bf(r2[2 * e], r2[2 * e + 1]);
+  }
+  *reinterpret_cast<u32x4_t*>(p + c * 8) = o1;
+  *reinterpret_cast<u32x4_t*>(p + D / 2 + c * 8) = o2;
+}
+
+// backward of the per-head norm alone (the attention backward has already rotated dq / dk back): in place on the q|k columns
+// of dqkv, dx = rstd * (g - xhat * mean_D(g * xhat)), g = w * dy, xhat = x * rstd, fp32 throughout; no weight gradient
+// (the LLM is frozen).  Same lane -> element map as the forward.
+template <int D>
+__global__ __launch_bounds__(256) void head_rmsnorm_bwd_kernel(
+    bf16_t* __restrict__ dqkv, int64_t ld, int col0, const bf16_t* __restrict__ x_in, const float* __restrict__ rstd_in,
+    const float* __restrict__ wq, const float* __restrict__ wk, int64_t M, int Hq, int H) {
+  constexpr int HC = D / 16;
+  const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool ok = item < M * H * HC;
+  const int c = (int)(item % HC);
+  const int64_t rh = ok ? item / HC : 0;
+  const int h = (int)(rh % H);
+  const int64_t row = rh / H;
+  bf16_t* p = dqkv + row * ld + col0 + h * D;
+  const bf16_t* xp = x_in + (row * H + h) * D;
+  u16x8_t g1 = {0, 0, 0, 0, 0, 0, 0, 0}, g2 = g1, x1 = g1, x2 = g1;
+  float rstd = 0.f;
+  if (ok) {
+    g1 = *reinterpret_cast<const u16x8_t*>(p + c * 8);
+    g2 = *reinterpret_cast<const u16x8_t*>(p + D / 2 + c * 8);
+    x1 = *reinterpret_cast<const u16x8_t*>(xp + c * 8);
+    x2 = *reinterpret_cast<const u16x8_t*>(xp + D / 2 + c * 8);
+    rstd = rstd_in[row * H + h];
+  }
+  const float* w = h < Hq ? wq : wk;
+  float w1[8], w2[8];
+  load8f(w + c * 8, w1);
+  load8f(w + D / 2 + c * 8, w2);
+  float ga[8], gb[8], xa[8], xb[8], dot = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    ga[e] = bf2f(g1[e]) * w1[e];
+    gb[e] = bf2f(g2[e]) * w2[e];
+    xa[e] = bf2f(x1[e]) * rstd;
+    xb[e] = bf2f(x2[e]) * rstd;
+    dot += ga[e] * xa[e];
+    dot += gb[e] * xb[e];
+  }
+  const float mdot = head_sum<HC>(dot) / (float)D;
+  if (!ok) return;
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+  u32x4_t o1, o2;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    o1[e] = pack2bf(rstd * (ga[2 * e] - xa[2 * e] * mdot), rstd * (ga[2 * e + 1] - xa[2 * e + 1] * mdot));
+    o2[e] = pack2bf(rstd * (gb[2 * e] - xb[2 * e] * mdot), rstd * (gb[2 * e + 1] - xb[2 * e + 1] * mdot));
+  }
+  *reinterpret_cast<u32x4_t*>(p + c * 8) = o1;
+  *reinterpret_cast<u32x4_t*>(p + D / 2 + c * 8) = o2;
+}
+
 }  // namespace
+
+/* HF Qwen3Attention.forward (transformers/models/qwen3/modeling_qwen3.py): query_states = q_norm(q_proj(x).view(.., D)),
+ * key_states = k_norm(k_proj(x).view(.., D)), then apply_rotary_pos_emb; the norm is Qwen3RMSNorm.forward. */
+extern "C" int slam_head_rmsnorm_rope(void* qkv, int64_t ld, int64_t col0, const float* q_weight, const float* k_weight,
+                                      float eps, const float* cos_table, const float* sin_table, const int32_t* positions,
+                                      float* rstd_out, void* x_out, int64_t B, int64_t T, int64_t Hq, int64_t Hkv, int64_t D,
+                                      void* stream) {
+  SLAM_CHECK_ARG(qkv && cos_table && sin_table, "slam_head_rmsnorm_rope: null pointer");
+  SLAM_CHECK_ARG(D == 64 || D == 128, "slam_head_rmsnorm_rope: head_dim %ld unsupported (64|128)", (long)D);
+  SLAM_CHECK_ARG(B > 0 && T > 0 && Hq >= 0 && Hkv >= 0 && Hq + Hkv > 0 && Hq + Hkv <= 65536, "slam_head_rmsnorm_rope: bad shape");
+  SLAM_CHECK_ARG((Hq == 0 || q_weight) && (Hkv == 0 || k_weight), "slam_head_rmsnorm_rope: null norm weight");
+  SLAM_CHECK_ARG(ld % 8 == 0 && col0 % 8 == 0 && col0 >= 0 && ld >= col0 + (Hq + Hkv) * D,
+                 "slam_head_rmsnorm_rope: ld/col0 must be multiples of 8 and the heads must fit in a row");
+  SLAM_CHECK_ARG((rstd_out == nullptr) == (x_out == nullptr), "slam_head_rmsnorm_rope: rstd/x outputs must both be set or both null");
+  const int64_t M = B * T, H = Hq + Hkv, blocks = cdiv64(M * H * (D / 16), 256);
+  SLAM_CHECK_ARG(blocks <= 0x7fffffffLL, "slam_head_rmsnorm_rope: too many rows");
+  if (D == 64)
+    hipLaunchKernelGGL(head_rmsnorm_rope_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, ld,
+                       (int)col0, q_weight, k_weight, eps, cos_table, sin_table, positions, rstd_out, (bf16_t*)x_out, M, (int)T,
+                       (int)Hq, (int)H);
+  else
+    hipLaunchKernelGGL(head_rmsnorm_rope_kernel<128>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, ld,
+                       (int)col0, q_weight, k_weight, eps, cos_table, sin_table, positions, rstd_out, (bf16_t*)x_out, M, (int)T,
+                       (int)Hq, (int)H);
+  SLAM_CHECK_LAUNCH("slam_head_rmsnorm_rope");
+  return 0;
+}
+
+extern "C" int slam_head_rmsnorm_bwd(void* dqkv, int64_t ld, int64_t col0, const void* x, const float* rstd,
+                                     const float* q_weight, const float* k_weight, int64_t M, int64_t Hq, int64_t Hkv,
+                                     int64_t D, void* stream) {
+  SLAM_CHECK_ARG(dqkv && x && rstd, "slam_head_rmsnorm_bwd: null pointer");
+  SLAM_CHECK_ARG(D == 64 || D == 128, "slam_head_rmsnorm_bwd: head_dim %ld unsupported (64|128)", (long)D);
+  SLAM_CHECK_ARG(M > 0 && Hq >= 0 && Hkv >= 0 && Hq + Hkv > 0 && Hq + Hkv <= 65536, "slam_head_rmsnorm_bwd: bad shape");
+  SLAM_CHECK_ARG((Hq == 0 || q_weight) && (Hkv == 0 || k_weight), "slam_head_rmsnorm_bwd: null norm weight");
+  SLAM_CHECK_ARG(ld % 8 == 0 && col0 % 8 == 0 && col0 >= 0 && ld >= col0 + (Hq + Hkv) * D,
+                 "slam_head_rmsnorm_bwd: ld/col0 must be multiples of 8 and the heads must fit in a row");
+  const int64_t H = Hq + Hkv, blocks = cdiv64(M * H * (D / 16), 256);
+  SLAM_CHECK_ARG(blocks <= 0x7fffffffLL, "slam_head_rmsnorm_bwd: too many rows");
+  if (D == 64)
+    hipLaunchKernelGGL(head_rmsnorm_bwd_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dqkv, ld,
+                       (int)col0, (const bf16_t*)x, rstd, q_weight, k_weight, M, (int)Hq, (int)H);
+  else
+    hipLaunchKernelGGL(head_rmsnorm_bwd_kernel<128>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dqkv, ld,
+                       (int)col0, (const bf16_t*)x, rstd, q_weight, k_weight, M, (int)Hq, (int)H);
+  SLAM_CHECK_LAUNCH("slam_head_rmsnorm_bwd");
+  return 0;
+}
 
 extern "C" int slam_layernorm_fwd(const void* x, int64_t ldx, const float* weight, const float* bias,
                                   void* y, int64_t ldy, int64_t M, int64_t d, float eps, int act, float* mean_out,

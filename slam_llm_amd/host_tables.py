@@ -12,10 +12,51 @@ def sinusoids(length: int, channels: int, max_timescale: float = 10000.0) -> tor
     return torch.cat([t.sin(), t.cos()], dim=1)
 
 
-def rope_tables(T: int, D: int, theta: float):
-    """HF LlamaRotaryEmbedding (default rope): cos/sin of pos * theta^(-2i/D), [T, D/2] fp32 each;
-    positions are arange(T) for every row because the reference never passes position_ids."""
+ROPE_SCALING_TYPES = ("default", "llama3", "linear")
+
+
+def rope_scaling_type(scaling) -> str:
+    """`rope_type` of an HF rope_scaling / rope_parameters dict (older configs spell the key `type`); None -> "default" """
+    if not scaling:
+        return "default"
+    return str(scaling.get("rope_type", scaling.get("type", "default")) or "default")
+
+
+def rope_inv_freq(D: int, theta: float, scaling=None) -> torch.Tensor:
+    """inverse frequencies [D/2] fp32.  scaling: None, or an HF rope_scaling dict of type
+      * `linear` (HF _compute_linear_scaling_rope_parameters): inv_freq / factor;
+      * `llama3` (HF _compute_llama3_parameters, Llama-3.1 / 3.2): wavelengths above original_max_position_embeddings / low_freq_factor
+        are divided by factor, those below original_max_position_embeddings / high_freq_factor stay, the band between is a smooth
+        interpolation of the two.
+    The operations and their order are HF's, so the result is bit-identical to the `inv_freq` buffer of the HF rotary module.
+    Any other type (yarn, dynamic, longrope, ...) raises."""
     inv = 1.0 / (theta ** (torch.arange(0, D, 2, dtype=torch.float32) / D))
+    kind = rope_scaling_type(scaling)
+    if kind == "default":
+        return inv
+    if kind == "linear":
+        return inv / scaling["factor"]
+    if kind == "llama3":
+        factor, low, high = scaling["factor"], scaling["low_freq_factor"], scaling["high_freq_factor"]
+        old_len = scaling["original_max_position_embeddings"]
+        low_wavelen, high_wavelen = old_len / low, old_len / high
+        wavelen = 2 * math.pi / inv
+        inv_l = torch.where(wavelen > low_wavelen, inv / factor, inv)
+        smooth = (old_len / wavelen - low) / (high - low)
+        smoothed = (1 - smooth) * inv_l / factor + smooth * inv_l
+        medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+        return torch.where(medium, smoothed, inv_l)
+    raise NotImplementedError(f"rope_scaling type {kind!r} is not implemented (the RoPE tables cover {list(ROPE_SCALING_TYPES)})")
+
+
+def rope_tables(T: int, D: int, theta: float, scaling=None):
+    """HF LlamaRotaryEmbedding: cos/sin of pos * inv_freq, [T, D/2] fp32 each (inv_freq = theta^(-2i/D), rescaled by `scaling`, see
+    rope_inv_freq; the attention factor of the covered types is 1); positions are arange(T) for every row because the reference never
+    passes position_ids."""
+    if not scaling:
+        inv = 1.0 / (theta ** (torch.arange(0, D, 2, dtype=torch.float32) / D))
+    else:
+        inv = rope_inv_freq(D, theta, scaling)
     fr = torch.arange(T, dtype=torch.float32)[:, None] * inv[None, :]
     return fr.cos().contiguous(), fr.sin().contiguous()
 

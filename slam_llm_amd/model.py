@@ -112,13 +112,29 @@ PRESETS.update({
     "qwen2.5-3b": dict(_QWEN2, llm_dim=2048, llm_layers=36, llm_heads=16, llm_kv_heads=2, llm_head_dim=128, llm_ffn=11008,
                        vocab=151936, tie_embeddings=True),
 })
+# Qwen3 (HF Qwen3ForCausalLM): no q/k/v bias, a per-head RMSNorm on q and k (llm_qk_norm), head_dim 128 whatever hidden_size / heads
+# is, the lm_head tied up to 4B.  Llama-3.1 / 3.2: the Llama-3 layout with the `llama3` RoPE frequency scaling.  From the public model
+# cards; the config.json of an HF llm_path directory wins over a preset.
+_QWEN3 = dict(rope_theta=1000000.0, rms_eps=1e-6, llm_qk_norm=True, llm_head_dim=128, vocab=151936)
+_LLAMA3_ROPE = dict(rope_type="llama3", low_freq_factor=1.0, high_freq_factor=4.0, original_max_position_embeddings=8192)
+PRESETS.update({
+    "qwen3-0.6b": dict(_QWEN3, llm_dim=1024, llm_layers=28, llm_heads=16, llm_kv_heads=8, llm_ffn=3072, tie_embeddings=True),
+    "qwen3-1.7b": dict(_QWEN3, llm_dim=2048, llm_layers=28, llm_heads=16, llm_kv_heads=8, llm_ffn=6144, tie_embeddings=True),
+    "qwen3-4b": dict(_QWEN3, llm_dim=2560, llm_layers=36, llm_heads=32, llm_kv_heads=8, llm_ffn=9728, tie_embeddings=True),
+    "qwen3-8b": dict(_QWEN3, llm_dim=4096, llm_layers=36, llm_heads=32, llm_kv_heads=8, llm_ffn=12288, tie_embeddings=False),
+    "llama-3.1-8b": dict(PRESETS["llama-3-8b"], rope_scaling=dict(_LLAMA3_ROPE, factor=8.0)),
+    "llama-3.2-1b": dict(llm_dim=2048, llm_layers=16, llm_heads=32, llm_kv_heads=8, llm_head_dim=64, llm_ffn=8192, vocab=128256,
+                         rope_theta=500000.0, rms_eps=1e-5, tie_embeddings=True, rope_scaling=dict(_LLAMA3_ROPE, factor=32.0)),
+    "llama-3.2-3b": dict(llm_dim=3072, llm_layers=28, llm_heads=24, llm_kv_heads=8, llm_head_dim=128, llm_ffn=8192, vocab=128256,
+                         rope_theta=500000.0, rms_eps=1e-5, tie_embeddings=True, rope_scaling=dict(_LLAMA3_ROPE, factor=32.0)),
+})
 
 
 def make_config(encoder: Optional[str] = None, llm: Optional[str] = None, **kw) -> dict:
     cfg = dict(n_mels=80, enc_dim=128, enc_heads=2, enc_layers=2, enc_ctx=1500, ds_rate=5, proj_hidden=2048,
                llm_dim=128, llm_layers=2, llm_heads=2, llm_kv_heads=1, llm_head_dim=64, llm_ffn=256, vocab=512,
-               rope_theta=10000.0, rms_eps=1e-5, llm_qkv_bias=False, tie_embeddings=False, lora_r=8, lora_alpha=32,
-               lora_targets=("q_proj", "v_proj"), lora_dropout=0.0)
+               rope_theta=10000.0, rms_eps=1e-5, llm_qkv_bias=False, tie_embeddings=False, llm_qk_norm=False, rope_scaling=None,
+               lora_r=8, lora_alpha=32, lora_targets=("q_proj", "v_proj"), lora_dropout=0.0)
     if encoder:
         cfg.update(PRESETS[encoder])
     if llm:
@@ -2117,7 +2133,10 @@ class HipLlamaLora(nn.Module):
     """Frozen Llama decoder + peft-style LoRA adapters (HF LlamaForCausalLM under peft's LoraModel as built at
     src/slam_llm/models/slam_model.py:118-221); parameter names follow peft 0.6.0.  Qwen2 (HF Qwen2ForCausalLM) is the same
     graph with cfg['llm_qkv_bias'] (a frozen bias on q/k/v_proj, added in the GEMM epilogue / the decode attention prologue) and
-    cfg['tie_embeddings'] (lm_head IS the input embedding)."""
+    cfg['tie_embeddings'] (lm_head IS the input embedding).  Qwen3 (HF Qwen3ForCausalLM) adds cfg['llm_qk_norm']: a frozen RMSNorm
+    over head_dim on every q and k head between the projection (+ LoRA delta) and RoPE, one fused launch with the RoPE in the training
+    forward and prefill, one launch in the backward, inside the attention kernel in decode.  cfg['rope_scaling'] (None or an HF
+    rope_scaling dict of type llama3 / linear) only changes the cos/sin tables."""
 
     ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
 
@@ -2136,12 +2155,14 @@ class HipLlamaLora(nn.Module):
         self.layers = []
         self.qkv_bias = bool(cfg.get("llm_qkv_bias", False))
         self.tied = bool(cfg.get("tie_embeddings", False))
+        self.qk_norm = bool(cfg.get("llm_qk_norm", False))
         targets = tuple(cfg.get("lora_targets") or ())
         r, alpha = cfg["lora_r"], cfg["lora_alpha"]
         P = prefix + "base_model.model."
         # reserve in backward-production order: last layer first
         for i in reversed(range(cfg["llm_layers"])):
-            L = SimpleNamespace(bias=None)     # bias: fp32 [(Hq + 2 Hkv) D] q|k|v bias (Qwen2) or None
+            # bias: fp32 [(Hq + 2 Hkv) D] q|k|v bias (Qwen2) or None; q_norm / k_norm: fp32 [D] per-head RMSNorm weights (Qwen3) or None
+            L = SimpleNamespace(bias=None, q_norm=None, k_norm=None)
             L.qkv = FusedLinear(d, [("q_proj", Hq * D), ("k_proj", Hkv * D), ("v_proj", Hkv * D)], device)
             L.o = FusedLinear(Hq * D, [("o_proj", d)], device)
             L.gu = FusedLinear(d, [("gate_proj", Fd), ("up_proj", Fd)], device)
@@ -2180,6 +2201,8 @@ class HipLlamaLora(nn.Module):
                 fl.finalize()
             if self.qkv_bias:
                 L.bias = torch.cat([f32(W[p + "self_attn." + n + ".bias"]) for n, _ in L.qkv.parts]).contiguous()
+            if self.qk_norm:
+                L.q_norm, L.k_norm = f32(W[p + "self_attn.q_norm.weight"]), f32(W[p + "self_attn.k_norm.weight"])
             L.ln1, L.ln2 = f32(W[p + "input_layernorm.weight"]), f32(W[p + "post_attention_layernorm.weight"])
         self.norm_w = f32(W[P + "model.norm.weight"])
         if self.tied:
@@ -2215,6 +2238,10 @@ class HipLlamaLora(nn.Module):
         if self.qkv_bias:   # drawn last: the draws of a bias-free config stay exactly as they were
             for L in self.layers:
                 L.bias = rn(L.qkv.N, std=0.5).to(torch.bfloat16).float()
+        if self.qk_norm:    # drawn after everything else, for the same reason
+            D = cfg["llm_head_dim"]
+            for L in self.layers:
+                L.q_norm, L.k_norm = 1 + rn(D, std=0.1), 1 + rn(D, std=0.1)
         return self
 
     def refresh(self):
@@ -2225,7 +2252,7 @@ class HipLlamaLora(nn.Module):
     def rope(self, T: int):
         if T not in self._rope:
             from .host_tables import rope_tables
-            cos, sin = rope_tables(T, self.cfg["llm_head_dim"], self.cfg["rope_theta"])
+            cos, sin = rope_tables(T, self.cfg["llm_head_dim"], self.cfg["rope_theta"], self.cfg.get("rope_scaling"))
             self._rope[T] = (cos.to(self.device_), sin.to(self.device_))
         return self._rope[T]
 
@@ -2278,7 +2305,12 @@ class HipLlamaLora(nn.Module):
             _, rstd1 = ops.rmsnorm_fwd(h, L.ln1, eps, out=x1[:, :d])
             dq_, do_, dg_, dd_ = drop_for(L.qkv), drop_for(L.o), drop_for(L.gu), drop_for(L.down)
             qkv = L.qkv.forward(x1, st, bias=L.bias, drop=dq_)
-            ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)     # q and k heads: adjacent columns, one launch
+            qk_rstd = qk_x = None
+            if self.qk_norm:    # Qwen3: per-head RMSNorm + RoPE in one launch; training keeps rstd and the pre-norm q|k for the backward
+                qk_rstd, qk_x = ops.head_rmsnorm_rope(qkv, 0, B, T, Hq, Hkv, D, L.q_norm, L.k_norm, eps, cos, sin, positions=positions,
+                                                      stash=train)
+            else:
+                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)     # q and k heads: adjacent columns, one launch
             o_ext = L.o.new_input(M)
             _, lse = ops.attn_fwd(qkv[:, : Hq * D], qkv[:, Hq * D: (Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:], B, T, Hq, Hkv, D, True, scale,
                                   key_mask=key_mask, want_lse=train, out=o_ext[:, : Hq * D], seg=seg)
@@ -2304,7 +2336,7 @@ class HipLlamaLora(nn.Module):
             if train:
                 stash["layers"].append(dict(h=h, rstd1=rstd1, x1=x1 if L.qkv.adapters else None, qkv=qkv,
                                             o=o_in, o_full=o_ext if pruned else None, inv=inv if pruned else None,
-                                            lse=lse, h_mid=h_mid, rstd2=rstd2,
+                                            lse=lse, h_mid=h_mid, rstd2=rstd2, qk_rstd=qk_rstd, qk_x=qk_x,
                                             x2=x2 if L.gu.adapters else None, gu=gu, gu_il=gu_il,
                                             hh=hh if L.down.adapters else None, drops=(dq_, do_, dg_, dd_)))
             h = h_out
@@ -2394,7 +2426,10 @@ class HipLlamaLora(nn.Module):
             x1 = L.qkv.new_input(M)
             ops.rmsnorm_fwd(h, L.ln1, eps, out=x1[:, :d])
             qkv = L.qkv.forward(x1, st, bias=L.bias)
-            ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)
+            if self.qk_norm:
+                ops.head_rmsnorm_rope(qkv, 0, B, T, Hq, Hkv, D, L.q_norm, L.k_norm, eps, cos, sin, positions=positions)
+            else:
+                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)
             cache.Kp[li].copy_(qkv[:, Hq * D:(Hq + Hkv) * D].view(B, T, Hkv * D))
             cache.Vp[li].copy_(qkv[:, (Hq + Hkv) * D:].view(B, T, Hkv * D))
             o_ext = L.o.new_input(M)
@@ -2413,7 +2448,7 @@ class HipLlamaLora(nn.Module):
     def _decode_body(self, cache) -> torch.Tensor:
         """one decode step over static buffers (cache.tok, cache.next_pos, cache.n_dev, cache.anc): every launch
         reads the step index from device memory, so the sequence can be captured once in a HIP graph and replayed.
-        7 launches per layer for <= 64 hypotheses: rmsnorm, qkv (+ LoRA A rows), attention (q|k|v bias + LoRA delta + RoPE + KV
+        7 launches per layer for <= 64 hypotheses: rmsnorm, qkv (+ LoRA A rows), attention (q|k|v bias + LoRA delta + per-head q/k RMSNorm + RoPE + KV
         append fused; the q|k|v GEMM itself never adds the bias), o_proj (+ residual), rmsnorm, gate_up (+ SwiGLU), down_proj (+ residual)."""
         cfg, st = self.cfg, self.store
         d, Hq, Hkv, D, Fd = cfg["llm_dim"], cfg["llm_heads"], cfg["llm_kv_heads"], cfg["llm_head_dim"], cfg["llm_ffn"]
@@ -2437,7 +2472,7 @@ class HipLlamaLora(nn.Module):
             o_ext = L.o.new_input(R)
             ops.attn_decode(qkv, lora_b, lora_r, cos, sin, cache.next_pos, cache.Kp[li], cache.Vp[li], cache.start,
                             cache.Kg[li], cache.Vg[li], cache.anc, cache.n_dev, cache.n, cache.beams, Hq, Hkv, D,
-                            D ** -0.5, o_ext, qkv_bias=L.bias)
+                            D ** -0.5, o_ext, qkv_bias=L.bias, qk_norm=(L.q_norm, L.k_norm, eps) if self.qk_norm else None)
             h_mid = L.o.forward(o_ext, st, residual=h)
             x2 = L.gu.new_input(R)
             ops.rmsnorm_fwd(h_mid, L.ln2, eps, out=x2[:, :d])
@@ -2547,6 +2582,8 @@ class HipLlamaLora(nn.Module):
                          dqkv[:, : Hq * D], dqkv[:, Hq * D: (Hq + Hkv) * D], dqkv[:, (Hq + Hkv) * D:],
                          B, T, Hq, Hkv, D, True, scale, key_mask=key_mask, rope=rope, seg=seg)  # RoPE backward fused
             del do_ext, dO
+            if self.qk_norm:    # dq / dk are gradients w.r.t. the normed, un-rotated heads: through the per-head RMSNorm, in place
+                ops.head_rmsnorm_bwd(dqkv, 0, S["qk_x"], S["qk_rstd"], Hq, Hkv, D, L.q_norm, L.k_norm)
             dx1 = L.qkv.backward(dqkv, S["x1"], st, accumulate, drop=dq_, defer=dfr)
             del dqkv
             dh = ops.rmsnorm_bwd(S["h"], S["rstd1"], L.ln1, dx1[:, :d], dres=dh_mid)
@@ -2785,6 +2822,7 @@ class SlamHipModel(nn.Module):
             self.encoder.refold_query_bias()
         for L in self.llm.layers:
             rnd(L.ln1); rnd(L.ln2)
+            rnd(L.q_norm); rnd(L.k_norm)     # Qwen3 per-head norm weights, like ln1
             rnd(L.bias)     # Qwen2 q|k|v bias: the reference rounds the bias itself; the kernels read the rounded value in fp32
         rnd(self.llm.norm_w)
 

@@ -530,6 +530,49 @@ def rope_inplace(src2d, col0, B, T, H, D, cos, sin, positions=None, inverse=Fals
     head_rope_transpose(src2d, col0, B, T, H, D, cos=cos, sin=sin, inverse=inverse, want_t=False, positions=positions)
 
 
+def _norm_w(w, H, D, name):
+    assert H == 0 or (w is not None and w.dtype == torch.float32 and w.is_contiguous() and w.numel() == D), \
+        f"{name}: expected a contiguous fp32 [{D}] norm weight"
+
+
+def head_rmsnorm_rope(src2d, col0, B, T, Hq, Hkv, D, q_weight, k_weight, eps, cos, sin, positions=None, stash=False):
+    """Qwen3: per-head RMSNorm (q_weight for the Hq first heads, k_weight for the Hkv next ones; fp32 [D]) then HF
+    apply_rotary_pos_emb, in place on columns [col0, col0 + (Hq + Hkv) * D) of src2d [B*T, ld] -- the fused launch that stands
+    where rope_inplace does for models without QK-norm.  stash=True (training) returns (rstd [B*T, Hq+Hkv] fp32, the pre-norm
+    columns [B*T, (Hq+Hkv)*D] bf16) for head_rmsnorm_bwd, else (None, None)."""
+    M, H = B * T, Hq + Hkv
+    assert src2d.dtype == torch.bfloat16 and src2d.shape[0] == M and col0 >= 0 and col0 + H * D <= src2d.shape[1]
+    assert D in (64, 128) and _ld(src2d) % 8 == 0 and col0 % 8 == 0
+    _norm_w(q_weight, Hq, D, "head_rmsnorm_rope")
+    _norm_w(k_weight, Hkv, D, "head_rmsnorm_rope")
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.shape == sin.shape and cos.shape[1] == D // 2 and (positions is not None or cos.shape[0] >= T)
+    assert positions is None or (positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == M)
+    rstd = torch.empty((M, H), dtype=torch.float32, device=src2d.device) if stash else None
+    x = torch.empty((M, H * D), dtype=torch.bfloat16, device=src2d.device) if stash else None
+    _timed("head_rmsnorm_rope", 0.0,
+           lambda: call("slam_head_rmsnorm_rope", _p(src2d), _ld(src2d), col0, _p(q_weight), _p(k_weight), eps, _p(cos), _p(sin),
+                        _p(positions), _p(rstd), _p(x), B, T, Hq, Hkv, D, _s()),
+           nbytes=(6.0 if stash else 4.0) * M * H * D)
+    return rstd, x
+
+
+def head_rmsnorm_bwd(dqkv, col0, x, rstd, Hq, Hkv, D, q_weight, k_weight):
+    """backward of the per-head RMSNorm, in place on the q|k columns of dqkv [M, ld] (gradients w.r.t. the post-norm, pre-RoPE
+    values, as attn_bwd with fused RoPE backward leaves them); x, rstd: head_rmsnorm_rope's stash.  The v columns stay."""
+    M, H = dqkv.shape[0], Hq + Hkv
+    assert dqkv.dtype == torch.bfloat16 and col0 >= 0 and col0 + H * D <= dqkv.shape[1] and _ld(dqkv) % 8 == 0 and col0 % 8 == 0
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and tuple(x.shape) == (M, H * D)
+    assert rstd.dtype == torch.float32 and rstd.is_contiguous() and tuple(rstd.shape) == (M, H) and D in (64, 128)
+    _norm_w(q_weight, Hq, D, "head_rmsnorm_bwd")
+    _norm_w(k_weight, Hkv, D, "head_rmsnorm_bwd")
+    _timed("head_rmsnorm_bwd", 0.0,
+           lambda: call("slam_head_rmsnorm_bwd", _p(dqkv), _ld(dqkv), col0, _p(x), _p(rstd), _p(q_weight), _p(k_weight), M, Hq, Hkv,
+                        D, _s()),
+           nbytes=(6.0 * D + 4.0) * M * H)
+    return dqkv
+
+
 def attn_needs_transposed(q2d, k2d, v2d, do2d, B, T, Tk, Hq, Hkv, D, drop=None, relpos=None) -> int:
     """bit 1: slam_attn_bwd reads Qt / Kt / dOt for this configuration (<= 64 queries, dropout, relative position bias, > 2 GiB)"""
     flags = (1 if drop else 0) | (2 if relpos else 0)
@@ -673,19 +716,25 @@ def attn_bwd(q2d, k2d, v2d, o2d, do2d, lse, dq2d, dk2d, dv2d, B, T, Hq, Hkv, D, 
 
 
 def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors,
-                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None):
+                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None, qk_norm=None):
     """one decode step of attention per hypothesis: (q|k|v bias +) LoRA delta + RoPE + KV append of the new token, then one
     query per row against [prompt KV of its batch item | generated KV via the ancestor table].  qkv_bias: fp32
-    [(Hq + 2 Hkv) D] (Qwen2) or None."""
+    [(Hq + 2 Hkv) D] (Qwen2) or None.  qk_norm: (q_weight, k_weight, eps), fp32 [D] each (Qwen3: per-head RMSNorm of the new q / k
+    behind bias and LoRA delta, before RoPE) or None."""
     R, G = k_gen.shape[0], k_gen.shape[1]
     Tp = k_prompt.shape[1]
     args = (_p(qkv), _ld(qkv), _p(lora_b), _ld(lora_b) if lora_b is not None else 0, lora_r, _p(cos), _p(sin), _p(positions),
             _p(k_prompt), _p(v_prompt), _p(prompt_start), _p(k_gen), _p(v_gen), _p(ancestors), _p(gen_count_dev), gen_count,
             _p(out), _ld(out), R, beams, Tp, G, Hq, Hkv, D, scale)
-    if qkv_bias is None:
+    if qkv_bias is not None:
+        assert qkv_bias.dtype == torch.float32 and qkv_bias.is_contiguous() and qkv_bias.numel() == (Hq + 2 * Hkv) * D
+    if qk_norm is not None:
+        _norm_w(qk_norm[0], Hq, D, "attn_decode")
+        _norm_w(qk_norm[1], Hkv, D, "attn_decode")
+        fn = lambda: call("slam_attn_decode_qknorm", *args, _p(qkv_bias), _p(qk_norm[0]), _p(qk_norm[1]), float(qk_norm[2]), _s())  # noqa: E731
+    elif qkv_bias is None:
         fn = lambda: call("slam_attn_decode", *args, _s())  # noqa: E731
     else:
-        assert qkv_bias.dtype == torch.float32 and qkv_bias.is_contiguous() and qkv_bias.numel() == (Hq + 2 * Hkv) * D
         fn = lambda: call("slam_attn_decode_bias", *args, _p(qkv_bias), _s())  # noqa: E731
     _timed("attn_decode", 4.0 * R * Hkv * D * (Tp + gen_count + 1), fn)
     return out

@@ -92,11 +92,31 @@ WAVLM_PRESETS["wavlm-base-plus"] = WAVLM_PRESETS["wavlm-base"]
 
 
 # ---------------------------------------------------------------------------------------------- Hugging Face LLM directories
-HF_LLM_TYPES = ("llama", "qwen2")
+HF_LLM_TYPES = ("llama", "qwen2", "qwen3")
+
+
+def hf_rope_scaling(hf_cfg: dict):
+    """the rope_scaling dict (make_config key `rope_scaling`) an HF config.json asks for, or None for plain RoPE.  Older configs carry
+    `rope_scaling`, newer ones `rope_parameters` (which also holds rope_theta); llama3 (Llama-3.1 / 3.2) and linear are implemented."""
+    from slam_llm_amd.host_tables import ROPE_SCALING_TYPES, rope_scaling_type
+    for key in ("rope_scaling", "rope_parameters"):
+        sc = hf_cfg.get(key) or {}
+        kind = rope_scaling_type(sc)
+        if kind == "default":
+            continue
+        if kind not in ROPE_SCALING_TYPES:
+            raise NotImplementedError(f"llm_path config.json: scaled RoPE of type {kind!r} is not implemented (the HIP LLM covers "
+                                      f"{[t for t in ROPE_SCALING_TYPES if t != 'default']})")
+        need = ("factor",) + (("low_freq_factor", "high_freq_factor", "original_max_position_embeddings") if kind == "llama3" else ())
+        missing = [k for k in need if sc.get(k) is None]
+        if missing:
+            raise ValueError(f"llm_path config.json: {key} of type {kind!r} lacks {missing}")
+        return dict({k: sc[k] for k in need}, rope_type=kind)
+    return None
 
 
 def hf_llm_geometry(hf_cfg: dict) -> dict:
-    """make_config keys of the decoder an HF `config.json` (LlamaForCausalLM / Qwen2ForCausalLM) describes"""
+    """make_config keys of the decoder an HF `config.json` (LlamaForCausalLM / Qwen2ForCausalLM / Qwen3ForCausalLM) describes"""
     mt = hf_cfg.get("model_type")
     if mt not in HF_LLM_TYPES:
         raise NotImplementedError(f"llm_path config.json: model_type {mt!r} is not implemented (the HIP LLM covers {list(HF_LLM_TYPES)})")
@@ -104,17 +124,19 @@ def hf_llm_geometry(hf_cfg: dict) -> dict:
         raise NotImplementedError("llm_path config.json: Llama with attention_bias / mlp_bias is not implemented")
     if hf_cfg.get("use_sliding_window"):
         raise NotImplementedError("llm_path config.json: sliding-window attention (use_sliding_window=true) is not implemented")
+    other = sorted({str(t) for t in (hf_cfg.get("layer_types") or []) if t != "full_attention"})
+    if other:
+        raise NotImplementedError(f"llm_path config.json: layer_types {other} are not implemented (every layer must be full_attention)")
     rope = hf_cfg.get("rope_parameters") or {}
-    scaling = hf_cfg.get("rope_scaling") or {}
-    if scaling.get("rope_type", scaling.get("type", "default")) != "default" or rope.get("rope_type", "default") != "default":
-        raise NotImplementedError("llm_path config.json: scaled RoPE (rope_scaling) is not implemented")
     theta = hf_cfg.get("rope_theta", rope.get("rope_theta", 10000.0))
     d, Hq = int(hf_cfg["hidden_size"]), int(hf_cfg["num_attention_heads"])
+    # Qwen2 always carries the q/k/v bias; Qwen3 has none unless attention_bias says so, and norms every q / k head (q_norm, k_norm)
+    bias = mt == "qwen2" or (mt == "qwen3" and bool(hf_cfg.get("attention_bias", False)))
     return dict(llm_dim=d, llm_layers=int(hf_cfg["num_hidden_layers"]), llm_heads=Hq,
                 llm_kv_heads=int(hf_cfg.get("num_key_value_heads") or Hq), llm_head_dim=int(hf_cfg.get("head_dim") or d // Hq),
                 llm_ffn=int(hf_cfg["intermediate_size"]), vocab=int(hf_cfg["vocab_size"]), rope_theta=float(theta),
-                rms_eps=float(hf_cfg.get("rms_norm_eps", 1e-6)), llm_qkv_bias=mt == "qwen2",
-                tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)))
+                rms_eps=float(hf_cfg.get("rms_norm_eps", 1e-6)), llm_qkv_bias=bias, llm_qk_norm=mt == "qwen3",
+                rope_scaling=hf_rope_scaling(hf_cfg), tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)))
 
 
 def read_hf_llm_config(llm_path):
