@@ -283,12 +283,42 @@ int slam_colsum_bf16(const void* x, int64_t ldx, float* out, int64_t M, int64_t 
 int slam_lora_pack_b(const float* B, float scale, void* dst, int64_t ld_dst, void* dstT, int64_t ld_dstT,
                      int64_t rows, int64_t r, void* stream);
 
+/* every adapter-derived operand of a model in ONE launch (after an optimizer step): per adapter what slam_lora_pack_b writes, per
+ * fused group what slam_transpose_bf16 writes for A -> A^T [K, Rp] (rows behind sum_r zero), bit-identical to those calls.
+ * table: DEVICE memory, n_items rows of 10 int64 words, ordered by word 9:
+ *   0 kind (0 pack B | 1 transpose A), 1 rows | sum_r, 2 r | K, 3 scale as fp32 bits (kind 0), 4 source (B fp32 [rows, r] | A bf16
+ *   [sum_r, K], contiguous; K % 8 == 0), 5 dst | A^T, 6 its leading dimension, 7 dstT (kind 0), 8 its leading dimension | Rp (kind 1,
+ *   a multiple of 64), 9 first workgroup of the item; a kind-1 item owns exactly (Rp / 64) * ceil(K / 64) workgroups, a kind-0 item
+ *   any number >= 1.  n_blocks = the workgroups of all items. */
+int slam_lora_refresh(const int64_t* table, int64_t n_items, int64_t n_blocks, void* stream);
+
 /* LoRA gradients (peft Linear backward): out[r*ld_r + c*ld_c] (+)= alpha * sum_m S[m,r] * X[m,c];
  * S [M,R] bf16 (R in 8|16|32|64), X [M,C] bf16, out fp32; workspace: slam_skinny_gram_workspace_bytes(M,R,C). */
 int64_t slam_skinny_gram_workspace_bytes(int64_t M, int64_t R, int64_t C);
 int slam_skinny_gram(const void* S, int64_t lds, const void* X, int64_t ldx, float* out, int64_t out_ld_r,
                      int64_t out_ld_c, int64_t M, int64_t R, int64_t C, float alpha, int accumulate, float drop_p,
                      uint64_t seed, uint64_t offset, float* workspace, void* stream);
+
+/* LoRA backward sweep (peft Linear backward of a group of projections sharing their input): one pass over dy [M, N] gives
+ *   dU[m, j] = sum_n dy[m, n] * Bt[j, n]   bf16 [M, Rp], columns [sum_r, Rp) written as zeros; Bt = (s B)^T stacked [Rp, N], zero
+ *                                          outside each adapter's columns (the K-extension rows of the fused transposed weight)
+ *   dB_a[n, j] (+)= scale_a * sum_m dy[m, row0_a + n] * U[m, j0_a + j]   fp32 [rows_a, r_a], row stride r_a -- what
+ *                                          slam_skinny_gram(U_a, dy_a, out_ld_r = 1, out_ld_c = r_a) deposits
+ * for up to 8 adapters; columns of dy outside every adapter's part are not read.  row0 and rows are multiples of 64, j0 the running sum
+ * of the ranks, sum_r a multiple of 8, Rp <= 64.  Partials are summed in a fixed order (no atomics).  splits: row splits (0 = automatic);
+ * workspace: slam_lora_bwd_sweep_workspace_bytes with the same M, N, sum_r, table and splits (-1: bad arguments). */
+typedef struct slam_lora_adapter {
+  int64_t row0, rows; /* the adapter's columns of dy */
+  int64_t j0, r;      /* its columns of U / dU */
+  float scale;        /* alpha / r */
+  float* dB;          /* gradient of lora_B, fp32 [rows, r] (unused by the workspace query) */
+} slam_lora_adapter;
+int64_t slam_lora_bwd_sweep_workspace_bytes(int64_t M, int64_t N, int64_t sum_r, const slam_lora_adapter* adapters,
+                                            int64_t n_adapters, int64_t splits);
+int slam_lora_bwd_sweep(const void* dy, int64_t ld_dy, const void* Bt, int64_t ld_bt, const void* U, int64_t ld_u, void* dU,
+                        int64_t ld_du, int64_t M, int64_t N, int64_t sum_r, int64_t Rp, const slam_lora_adapter* adapters,
+                        int64_t n_adapters, int accumulate, int64_t splits, float* workspace, int64_t workspace_bytes,
+                        void* stream);
 
 /* LoRA first hop u[M, R] = lora_dropout(x)[M, K] . A[R, K]^T (peft 0.6.0 Linear.forward: lora_A(lora_dropout(x))), R <= 64
  * = all adapters sharing x stacked.  drop_p > 0 applies the counter-based mask of slam_dropout_bf16 (same seed / offset /

@@ -512,6 +512,73 @@ __global__ __launch_bounds__(256) void lora_pack_b_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------
+// One launch for every adapter-derived operand of a model (after the optimizer step): the work of one lora_pack_b_kernel per adapter
+// and one transpose_kernel (A -> A^T, zero-padded) per fused group, walked from a table in device memory.  Bit-identical to those.
+// Table: n_items rows of 10 int64 words, ordered by first block:
+//   [0] kind: 0 = pack B, 1 = transpose A      [1] rows | sum_r     [2] r | K      [3] scale (fp32 bits; kind 0)
+//   [4] source: B fp32 [rows, r] contiguous | A bf16 [sum_r, K] contiguous
+//   [5] dst [rows, r] view | A^T [K, Rp]       [6] its leading dimension
+//   [7] dstT [r, rows] view (kind 0)           [8] its leading dimension | Rp (kind 1)
+//   [9] first block of the item (the item's blocks end where the next item's begin; the last one's at gridDim.x)
+// ------------------------------------------------------------------------------------------
+constexpr int RF_WORDS = 10;
+
+__global__ __launch_bounds__(256) void lora_refresh_kernel(const int64_t* __restrict__ tab, int n_items) {
+  constexpr int LDT = 64 + 8;
+  __shared__ __attribute__((aligned(16))) bf16_t tile[64 * LDT];
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  int lo = 0, hi = n_items - 1;   // last item whose first block is <= blk
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int)tab[(int64_t)mid * RF_WORDS + 9] <= blk) lo = mid;
+    else hi = mid - 1;
+  }
+  const int64_t* it = tab + (int64_t)lo * RF_WORDS;
+  const int b0 = (int)it[9];
+  const int nb = (lo + 1 < n_items ? (int)tab[(int64_t)(lo + 1) * RF_WORDS + 9] : (int)gridDim.x) - b0;
+  const int t = blk - b0;
+  if (it[0] == 0) {   // lora_pack_b_kernel
+    const float* B = reinterpret_cast<const float*>(it[4]);
+    const float scale = __int_as_float((int)it[3]);
+    bf16_t* dst = reinterpret_cast<bf16_t*>(it[5]);
+    bf16_t* dstT = reinterpret_cast<bf16_t*>(it[7]);
+    const int64_t ld_dst = it[6], ld_dstT = it[8];
+    const int r = (int)it[2];
+    const int64_t total = it[1] * r;
+    for (int64_t i = t * 256ll + tid; i < total; i += (int64_t)nb * 256) {
+      const int64_t row = i / r;
+      const int j = (int)(i % r);
+      const bf16_t v = f2bf(B[i] * scale);
+      dst[row * ld_dst + j] = v;
+      dstT[(int64_t)j * ld_dstT + row] = v;
+    }
+    return;
+  }
+  // transpose_kernel: in [R, C] -> out [C, Rp], rows R..Rp-1 written as zeros
+  const bf16_t* in = reinterpret_cast<const bf16_t*>(it[4]);
+  bf16_t* out = reinterpret_cast<bf16_t*>(it[5]);
+  const int R = (int)it[1], C = (int)it[2];
+  const int64_t ldi = C, ldo = it[6];
+  const int nbx = (int)(it[8] / 64);
+  const int r0 = (t % nbx) * 64, c0 = (t / nbx) * 64;
+  for (int item = tid; item < 512; item += 256) {
+    const int r = item >> 3, cc = item & 7;
+    u16x8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r0 + r < R && c0 + cc * 8 < C) v = *reinterpret_cast<const u16x8_t*>(in + (int64_t)(r0 + r) * ldi + c0 + cc * 8);
+    *reinterpret_cast<u16x8_t*>(&tile[r * LDT + cc * 8]) = v;
+  }
+  __syncthreads();
+  for (int item = tid; item < 512; item += 256) {
+    const int c = item >> 3, rc = item & 7;
+    if (c0 + c >= C) continue;
+    u16x8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; e++) o[e] = tile[(rc * 8 + e) * LDT + c];
+    *reinterpret_cast<u16x8_t*>(out + (int64_t)(c0 + c) * ldo + r0 + rc * 8) = o;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // column sum (bias gradients of the projector Linears): out[n] (+)= sum_m x[m, n], deterministic order
 // one workgroup = 64 columns; thread (ty = tid/8, tx = tid%8) walks rows ty, ty+32, ... on 8 columns
 // ------------------------------------------------------------------------------------------
@@ -1165,6 +1232,14 @@ extern "C" int slam_relu_bwd(void* dh, int64_t lddh, const void* h, int64_t ldh,
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(M * (N / 8))), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)dh, lddh, (const bf16_t*)h, ldh, M, (int)N);
   SLAM_CHECK_LAUNCH("slam_relu_bwd");
+  return 0;
+}
+
+extern "C" int slam_lora_refresh(const int64_t* table, int64_t n_items, int64_t n_blocks, void* stream) {
+  SLAM_CHECK_ARG(table && ((uintptr_t)table % 8) == 0, "slam_lora_refresh: null or misaligned table");
+  SLAM_CHECK_ARG(n_items > 0 && n_blocks >= n_items && n_blocks < (1ll << 31), "slam_lora_refresh: need 1 <= n_items <= n_blocks < 2^31");
+  hipLaunchKernelGGL(lora_refresh_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, (int)n_items);
+  SLAM_CHECK_LAUNCH("slam_lora_refresh");
   return 0;
 }
 

@@ -528,6 +528,273 @@ __global__ __launch_bounds__(256) void skinny_gram_reduce_kernel(const float* __
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// LoRA backward sweep: ONE pass over dy gives both products that reduce it (peft Linear backward of a fused group):
+//   du[m, j]        = sum_n dy[m, n] * Bt[j, n]            Bt = (s B)^T = WextT[K:], zero outside each adapter's columns
+//   dB_a[n, j] (+)= s_a * sum_m dy[m, row0_a + n] * u[m, j0_a + j]
+// The N = Rp extension product fetched dy in MFMA-fragment order (64-128-byte pieces per row) and the per-adapter dB grams
+// streamed the same dy a second time; the columns of parts without an adapter were read for a product with zeros.
+// Plan:
+//   * a workgroup owns a BAND of up to 1024 columns (4 waves x 256) inside one adapter's part and a range of rows, walked in
+//     32-row tiles.  Adapters of rank > 32 are cut into chunks of <= 32 ranks (each chunk sweeps the part once more; the
+//     accumulators of more ranks do not fit beside a 1024-column band).
+//   * a tile is fetched row-major -- one wave-instruction reads 1 KiB of one row -- into registers (16 x 16 bytes per thread
+//     in flight under the previous tile's MFMAs) and staged in LDS with the row stride of gram_mfma_kernel's staging (+32
+//     bytes: consecutive rows shift by 8 banks).
+//   * du: the staged tile is the M x k operand (16-byte LDS reads), the (s B)^T fragments of the wave's 256 columns stay in
+//     registers for the whole sweep; the 4 waves' partials meet in LDS in wave order, and the band's partial goes to the
+//     workspace in fp32.  Only parts wider than one band (q: 4 bands) have more than one partial per du element.
+//   * dB: transposed fragments gathered from the same staged tile like gram_mfma_kernel does, accumulated in registers over
+//     the workgroup's rows, one fp32 partial per row split.
+//   * row splits: as many as fill 2 workgroups per CU (75 KiB of LDS each at rank <= 16), but never shorter than 8 r rows, so that the
+//     dB partials (4 r bytes per column and split) stay under a quarter of the dy bytes (2 bytes per column and row).
+//     Llama-3-8B q|v, r 16, M 11780: 5 bands x 93 splits of 128 rows = 465 workgroups, dB partials 25 % of the dy bytes (12.5 % at r 8).
+//   * lora_bwd_sweep_finish_kernel adds the partials in FIXED order (bands for du, splits for dB; no atomics: repeats are
+//     bit-equal), rounds du to bf16 once, zeroes the padding columns [sum_r, Rp) and deposits s * dB in the gradient views.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int SW_BAND = 1024;            // columns of dy per workgroup
+constexpr int SW_XLD = SW_BAND + 16;     // 2080-byte rows = 520 dwords: consecutive rows shift by 8 banks
+constexpr int SW_MAXC = 10;              // chunks: <= 8 adapters, and sum_r <= 64 lets at most one of them exceed 32 ranks
+
+struct SweepChunk {
+  int col0, cols;        // the adapter's part of dy
+  int j0, r;             // its columns of u / du (r <= 32)
+  int band0, nb;         // first blockIdx.x, number of bands
+  float scale;
+  float* dB;             // &dB_a[0, j0 - j0_a]
+  int64_t ldb;           // the adapter's full rank
+  int64_t ws_du, ws_db;  // float offsets into the workspace: [nb][M][r] and [nsplit][r][cols]
+};
+struct SweepTable {
+  int nchunk;
+  SweepChunk c[SW_MAXC];
+};
+
+template <int NJ>
+constexpr int sweep_lds_bytes() {
+  return 32 * SW_XLD * 2 + 32 * (NJ == 1 ? 16 : 48) * 2 + 4 * 32 * 16 * NJ * 4;
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256, NJ == 1 ? 2 : 1) void lora_bwd_sweep_kernel(const bf16_t* __restrict__ dy, int64_t ldy,
+                                                             const bf16_t* __restrict__ bt, int64_t ldbt,
+                                                             const bf16_t* __restrict__ u, int64_t ldu,
+                                                             float* __restrict__ ws, const SweepTable tab, int M,
+                                                             int rows_per_split) {
+  constexpr int ULD = NJ == 1 ? 16 : 48;   // dword strides 8 / 24: 4 consecutive rows -> disjoint banks (as gram_mfma_kernel)
+  constexpr int RW = 16 * NJ;
+  extern __shared__ __attribute__((aligned(16))) char sw_lds[];
+  bf16_t* xs = reinterpret_cast<bf16_t*>(sw_lds);
+  bf16_t* us = xs + 32 * SW_XLD;
+  float* red = reinterpret_cast<float*>(us + 32 * ULD);   // [wave][row][RW]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, g = lane >> 4;
+
+  SweepChunk ch = tab.c[0];
+#pragma unroll
+  for (int k = 1; k < SW_MAXC; k++)
+    if (k < tab.nchunk && (int)blockIdx.x >= tab.c[k].band0) ch = tab.c[k];
+  const int band = (int)blockIdx.x - ch.band0;
+  const int bcol = band * SW_BAND;                     // first column of the band inside the part
+  const int bcols = min(SW_BAND, ch.cols - bcol);      // its width (a multiple of 64)
+  const bf16_t* dyb = dy + ch.col0 + bcol;
+  const int m0 = blockIdx.y * rows_per_split, m1 = min(M, m0 + rows_per_split);
+  const int wc0 = wave * 256;                          // the wave's columns inside the band
+  const bool active = wc0 < bcols;
+
+  // (s B)^T fragments of the wave's columns: lane (li, g) holds Bt[j0 + jt*16 + li][wc0 + ks*32 + g*8 .. +8]
+  u16x8_t bfrag[8][NJ];
+#pragma unroll
+  for (int ks = 0; ks < 8; ks++)
+#pragma unroll
+    for (int jt = 0; jt < NJ; jt++) {
+      const int j = jt * 16 + li, c = wc0 + ks * 32 + g * 8;
+      u16x8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (j < ch.r && c < bcols) v = *reinterpret_cast<const u16x8_t*>(bt + (int64_t)(ch.j0 + j) * ldbt + ch.col0 + bcol + c);
+      bfrag[ks][jt] = v;
+    }
+
+  f32x4_t adb[NJ][16], adu[2][NJ];
+#pragma unroll
+  for (int jt = 0; jt < NJ; jt++) {
+#pragma unroll
+    for (int t = 0; t < 16; t++) adb[jt][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    adu[0][jt] = adu[1][jt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  u16x8_t xreg[16];
+  bf16_t ureg[2 * NJ];
+  auto gload = [&](int mb) {
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int id = tid + i * 256, row = id >> 7, cc = id & 127;
+      const int m = mb + row;
+      u16x8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (m < m1 && cc * 8 < bcols) v = *reinterpret_cast<const u16x8_t*>(dyb + (int64_t)m * ldy + cc * 8);
+      xreg[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * NJ; i++) {
+      const int row = tid >> 3, j = (tid & 7) + 8 * i;
+      const int m = mb + row;
+      ureg[i] = (m < m1 && j < ch.r) ? u[(int64_t)m * ldu + ch.j0 + j] : (bf16_t)0;
+    }
+  };
+  auto lstore = [&]() {
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int id = tid + i * 256, row = id >> 7, cc = id & 127;
+      *reinterpret_cast<u16x8_t*>(&xs[row * SW_XLD + cc * 8]) = xreg[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * NJ; i++) us[(tid >> 3) * ULD + (tid & 7) + 8 * i] = ureg[i];
+  };
+  // the band's du partial of the tile at mb: the 4 waves' contributions in wave order -> workspace [band][m][r]
+  float* wdu = ws + ch.ws_du + (int64_t)band * M * ch.r;
+  auto flush_du = [&](int mb) {
+    for (int id = tid; id < 32 * ch.r; id += 256) {
+      const int row = id / ch.r, j = id - row * ch.r;
+      const int m = mb + row;
+      if (m < m1) {
+        const float* p = red + row * RW + j;
+        wdu[(int64_t)m * ch.r + j] = ((p[0] + p[32 * RW]) + p[2 * 32 * RW]) + p[3 * 32 * RW];
+      }
+    }
+  };
+
+  if (m0 < m1) gload(m0);
+  for (int mb = m0; mb < m1; mb += 32) {
+    __syncthreads();
+    lstore();
+    if (mb > m0) flush_du(mb - 32);
+    __syncthreads();
+    if (mb + 32 < m1) gload(mb + 32);
+    if (active) {
+      // du: rows of the tile x the wave's 256 columns (k); k-slot (g, e) <-> column ks*32 + g*8 + e for both operands
+#pragma unroll
+      for (int ks = 0; ks < 8; ks++)
+#pragma unroll
+        for (int rt = 0; rt < 2; rt++) {
+          const u16x8_t a = *reinterpret_cast<const u16x8_t*>(&xs[(rt * 16 + li) * SW_XLD + wc0 + ks * 32 + g * 8]);
+#pragma unroll
+          for (int jt = 0; jt < NJ; jt++)
+            adu[rt][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
+                                                                  __builtin_bit_cast(bf16x8_t, bfrag[ks][jt]), adu[rt][jt], 0, 0, 0);
+        }
+      // dB: k-slot (g, e) <-> tile row e*4 + g for both operands (gram_mfma_kernel's gather)
+      u16x8_t af[NJ];
+#pragma unroll
+      for (int jt = 0; jt < NJ; jt++)
+#pragma unroll
+        for (int e = 0; e < 8; e++) af[jt][e] = us[(e * 4 + g) * ULD + jt * 16 + li];
+#pragma unroll
+      for (int t = 0; t < 16; t++) {
+        u16x8_t bfr;
+#pragma unroll
+        for (int e = 0; e < 8; e++) bfr[e] = xs[(e * 4 + g) * SW_XLD + wc0 + t * 16 + li];
+#pragma unroll
+        for (int jt = 0; jt < NJ; jt++)
+          adb[jt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[jt]),
+                                                               __builtin_bit_cast(bf16x8_t, bfr), adb[jt][t], 0, 0, 0);
+      }
+    }
+    // adu[rt][jt][i] = du[row rt*16 + 4g + i][j = jt*16 + li] over the wave's columns (inactive waves: zeros)
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+      for (int jt = 0; jt < NJ; jt++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) red[(wave * 32 + rt * 16 + 4 * g + i) * RW + jt * 16 + li] = adu[rt][jt][i];
+        adu[rt][jt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      }
+  }
+  if (m0 < m1) {
+    __syncthreads();
+    flush_du(m0 + ((m1 - m0 - 1) / 32) * 32);
+  }
+  // adb[jt][t][i] = partial dB^T[j = jt*16 + 4g + i][n = bcol + wc0 + t*16 + li] -> workspace [split][r][cols]
+  if (active) {
+    float* w = ws + ch.ws_db + (int64_t)blockIdx.y * ch.r * ch.cols;
+#pragma unroll
+    for (int jt = 0; jt < NJ; jt++)
+#pragma unroll
+      for (int t = 0; t < 16; t++) {
+        const int c = wc0 + t * 16 + li;
+        if (c >= bcols) continue;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int j = jt * 16 + 4 * g + i;
+          if (j < ch.r) w[(int64_t)j * ch.cols + bcol + c] = adb[jt][t][i];
+        }
+      }
+  }
+}
+
+// fixed-order sums of the sweep's partials.  Blocks [0, db_blocks): dB_a[n, j] (+)= s_a * (sum over the row splits), one element per
+// thread and chunk, the partial loads 32 deep in flight (the launch is latency-bound: 93 partials per element at the Llama q|v shape) while
+// the adds stay in split order (slots past the last split add 0.f); the other blocks: du[m, j] = bf16(sum over the bands of j's chunk), zeros in the padding columns
+__global__ __launch_bounds__(256) void lora_bwd_sweep_finish_kernel(const float* __restrict__ ws, bf16_t* __restrict__ du,
+                                                                    int64_t lddu, const SweepTable tab, int M, int Rp,
+                                                                    int nsplit, int accumulate, int db_blocks) {
+  if ((int)blockIdx.x >= db_blocks) {
+    const int64_t id = ((int64_t)blockIdx.x - db_blocks) * 256 + threadIdx.x;
+    if (id >= (int64_t)M * Rp) return;
+    const int m = (int)(id / Rp), j = (int)(id % Rp);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < SW_MAXC; k++) {
+      if (k < tab.nchunk && j >= tab.c[k].j0 && j < tab.c[k].j0 + tab.c[k].r) {
+        const int r = tab.c[k].r;
+        const float* p = ws + tab.c[k].ws_du + (int64_t)m * r + (j - tab.c[k].j0);
+        for (int b0 = 0; b0 < tab.c[k].nb; b0 += 4) {   // 4 partials requested together, added in band order (+ 0.f past the last)
+          float v[4];
+#pragma unroll
+          for (int i = 0; i < 4; i++) v[i] = b0 + i < tab.c[k].nb ? p[(int64_t)(b0 + i) * M * r] : 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; i++) s += v[i];
+        }
+      }
+    }
+    du[(int64_t)m * lddu + j] = f2bf(s);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < SW_MAXC; k++) {
+    const int r = tab.c[k].r, cols = tab.c[k].cols;
+    const int64_t total = k < tab.nchunk ? (int64_t)r * cols : 0;
+    const float* p0 = ws + tab.c[k].ws_db;
+    for (int64_t id = blockIdx.x * 256ll + threadIdx.x; id < total; id += (int64_t)db_blocks * 256) {
+      float s = 0.f;
+      for (int q0 = 0; q0 < nsplit; q0 += 32) {   // whole groups of 32 requested together (a remainder loop would wait for each load in turn)
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 32; i++) v[i] = q0 + i < nsplit ? p0[(int64_t)(q0 + i) * total + id] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; i++) s += v[i];
+      }
+      const int j = (int)(id / cols), n = (int)(id % cols);
+      float* o = tab.c[k].dB + (int64_t)n * tab.c[k].ldb + j;
+      *o = accumulate ? (*o + tab.c[k].scale * s) : tab.c[k].scale * s;
+    }
+  }
+}
+
+// rows per split and number of splits (splits > 0: forced, the rows cut evenly)
+void sweep_plan(int64_t M, int64_t total_bands, int64_t rmax, int64_t splits, int* rows_per_split, int* nsplit) {
+  int64_t rps;
+  if (splits > 0) {
+    rps = cdiv64(M, splits);
+  } else {
+    int64_t ns = 512 / total_bands;
+    if (ns < 1) ns = 1;
+    rps = cdiv64(cdiv64(M, ns), 32) * 32;
+    const int64_t floor_rows = cdiv64(8 * rmax, 32) * 32;
+    if (rps < floor_rows) rps = floor_rows;
+  }
+  *rows_per_split = (int)rps;
+  *nsplit = (int)cdiv64(M, rps);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // LoRA first hop  u[M, R] = dropout(x)[M, K] . A[R, K]^T   (peft: lora_A(lora_dropout(x)), R = sum of the ranks of the
 // adapters sharing x, <= 64).  HBM-bound on x: a 128-row MFMA GEMM tile gives only M/128 workgroups (93 for the C3
 // batch) -- here a workgroup owns 32 rows and its 4 waves split K (fixed-order LDS reduction), the dropout mask is
@@ -833,5 +1100,124 @@ extern "C" int slam_skinny_gram(const void* S, int64_t lds_, const void* X, int6
   hipLaunchKernelGGL(skinny_gram_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, workspace, out, out_ld_r, out_ld_c,
                      (int)R, (int)C, nsplit, alpha, accumulate);
   SLAM_CHECK_LAUNCH("slam_skinny_gram");
+  return 0;
+}
+
+// the adapter table of slam_lora_bwd_sweep as include/slam_hip.h declares it
+struct slam_lora_adapter {
+  int64_t row0, rows;   // the adapter's columns of dy
+  int64_t j0, r;        // its columns of u / du
+  float scale;
+  float* dB;            // fp32 [rows, r], row stride r
+};
+
+namespace {
+
+// validates the table and cuts it into chunks of <= 32 ranks; returns 0 or -1 (error set)
+int sweep_table(const char* who, int64_t M, int64_t N, int64_t sum_r, const slam_lora_adapter* ad, int64_t n, int64_t splits,
+                bool need_out, SweepTable* tab, int* rows_per_split, int* nsplit, int* nj, int64_t* ws_floats) {
+  SLAM_CHECK_ARG(ad, "%s: null pointer", who);
+  SLAM_CHECK_ARG(n >= 1 && n <= 8, "%s: 1..8 adapters (got %lld)", who, (long long)n);
+  SLAM_CHECK_ARG(M > 0 && M < (1ll << 31) && splits >= 0, "%s: bad M / splits", who);
+  int64_t j = 0, rmax = 0, bands = 0;
+  tab->nchunk = 0;
+  for (int64_t a = 0; a < n; a++) {
+    SLAM_CHECK_ARG(ad[a].rows > 0 && ad[a].row0 >= 0 && ad[a].row0 % 64 == 0 && ad[a].rows % 64 == 0 && ad[a].row0 + ad[a].rows <= N,
+                   "%s: adapter %lld: row0=%lld and rows=%lld must be multiples of 64 inside N=%lld", who, (long long)a,
+                   (long long)ad[a].row0, (long long)ad[a].rows, (long long)N);
+    SLAM_CHECK_ARG(ad[a].r > 0 && ad[a].j0 == j, "%s: adapter %lld: ranks must be positive and j0 the running sum of the ranks", who, (long long)a);
+    SLAM_CHECK_ARG(!need_out || ad[a].dB, "%s: null pointer (dB of adapter %lld)", who, (long long)a);
+    for (int64_t jc = 0; jc < ad[a].r; jc += 32) {
+      SweepChunk& c = tab->c[tab->nchunk++];
+      c.col0 = (int)ad[a].row0;
+      c.cols = (int)ad[a].rows;
+      c.j0 = (int)(j + jc);
+      c.r = (int)(ad[a].r - jc < 32 ? ad[a].r - jc : 32);
+      c.band0 = (int)bands;
+      c.nb = (int)cdiv64(ad[a].rows, SW_BAND);
+      c.scale = ad[a].scale;
+      c.dB = ad[a].dB ? ad[a].dB + jc : nullptr;
+      c.ldb = ad[a].r;
+      bands += c.nb;
+      if (c.r > rmax) rmax = c.r;
+      if (tab->nchunk == SW_MAXC && (jc + 32 < ad[a].r || a + 1 < n)) {
+        slam_set_error("%s: more than %d rank chunks", who, SW_MAXC);
+        return -1;
+      }
+    }
+    j += ad[a].r;
+  }
+  SLAM_CHECK_ARG(j == sum_r && sum_r % 8 == 0 && sum_r <= 64, "%s: sum_r=%lld must be the sum of the ranks, a multiple of 8, <= 64", who, (long long)sum_r);
+  sweep_plan(M, bands, rmax, splits, rows_per_split, nsplit);
+  *nj = rmax <= 16 ? 1 : 2;
+  int64_t off = 0;
+  for (int k = 0; k < tab->nchunk; k++) {
+    SweepChunk& c = tab->c[k];
+    c.ws_du = off;
+    off += (int64_t)c.nb * M * c.r;
+    c.ws_db = off;
+    off += (int64_t)*nsplit * c.r * c.cols;
+    off = (off + 3) / 4 * 4;
+  }
+  *ws_floats = off;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t slam_lora_bwd_sweep_workspace_bytes(int64_t M, int64_t N, int64_t sum_r, const slam_lora_adapter* adapters,
+                                                       int64_t n_adapters, int64_t splits) {
+  SweepTable tab;
+  int rps, nsplit, nj;
+  int64_t wsf;
+  if (sweep_table("slam_lora_bwd_sweep_workspace_bytes", M, N, sum_r, adapters, n_adapters, splits, false, &tab, &rps, &nsplit, &nj, &wsf))
+    return -1;
+  return wsf * (int64_t)sizeof(float);
+}
+
+extern "C" int slam_lora_bwd_sweep(const void* dy, int64_t ld_dy, const void* Bt, int64_t ld_bt, const void* U, int64_t ld_u,
+                                   void* dU, int64_t ld_du, int64_t M, int64_t N, int64_t sum_r, int64_t Rp,
+                                   const slam_lora_adapter* adapters, int64_t n_adapters, int accumulate, int64_t splits,
+                                   float* workspace, int64_t workspace_bytes, void* stream) {
+  SLAM_CHECK_ARG(dy && Bt && U && dU && adapters && workspace, "slam_lora_bwd_sweep: null pointer");
+  SLAM_CHECK_ARG(Rp > 0 && Rp <= 64 && Rp >= sum_r && ld_du >= Rp, "slam_lora_bwd_sweep: Rp=%lld must be in [sum_r, 64] and <= ld_du", (long long)Rp);
+  SLAM_CHECK_ARG(N > 0 && N % 64 == 0 && ld_dy >= N && ld_bt >= N && ld_dy % 8 == 0 && ld_bt % 8 == 0 && ld_u >= sum_r,
+                 "slam_lora_bwd_sweep: N must be a multiple of 64, ld_dy / ld_bt multiples of 8 and >= N, ld_u >= sum_r");
+  SLAM_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)Bt % 16) == 0 && ((uintptr_t)workspace % 16) == 0,
+                 "slam_lora_bwd_sweep: dy / Bt / workspace must be 16-byte aligned");
+  SweepTable tab;
+  int rps, nsplit, nj;
+  int64_t wsf;
+  if (sweep_table("slam_lora_bwd_sweep", M, N, sum_r, adapters, n_adapters, splits, true, &tab, &rps, &nsplit, &nj, &wsf)) return -1;
+  SLAM_CHECK_ARG(workspace_bytes >= wsf * (int64_t)sizeof(float), "slam_lora_bwd_sweep: workspace too small (need %lld bytes)",
+                 (long long)(wsf * (int64_t)sizeof(float)));
+  const SweepChunk& last = tab.c[tab.nchunk - 1];
+  dim3 grid((unsigned)(last.band0 + last.nb), (unsigned)nsplit);
+  hipStream_t s = (hipStream_t)stream;
+#define SLAM_LAUNCH_SW(NJ_)                                                                                                          \
+  do {                                                                                                                               \
+    auto kern = lora_bwd_sweep_kernel<NJ_>;                                                                                          \
+    constexpr int lds = sweep_lds_bytes<NJ_>();                                                                                      \
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {   \
+      slam_set_error("slam_lora_bwd_sweep: cannot raise the LDS limit to %d", lds);                                                  \
+      return -2;                                                                                                                     \
+    }                                                                                                                                \
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, (const bf16_t*)dy, ld_dy, (const bf16_t*)Bt, ld_bt, (const bf16_t*)U, ld_u,   \
+                       workspace, tab, (int)M, rps);                                                                                 \
+  } while (0)
+  if (nj == 1) SLAM_LAUNCH_SW(1);
+  else SLAM_LAUNCH_SW(2);
+#undef SLAM_LAUNCH_SW
+  SLAM_CHECK_LAUNCH("slam_lora_bwd_sweep");
+  const int64_t du_blocks = cdiv64(M * Rp, 256);
+  int64_t db_total = 0;
+  for (int k = 0; k < tab.nchunk; k++)
+    if ((int64_t)tab.c[k].r * tab.c[k].cols > db_total) db_total = (int64_t)tab.c[k].r * tab.c[k].cols;
+  int64_t db_blocks = cdiv64(db_total, 256);
+  if (db_blocks > 4096) db_blocks = 4096;
+  SLAM_CHECK_ARG(du_blocks + db_blocks < (1ll << 31), "slam_lora_bwd_sweep: M too large");
+  hipLaunchKernelGGL(lora_bwd_sweep_finish_kernel, dim3((unsigned)(du_blocks + db_blocks)), dim3(256), 0, s, workspace, (bf16_t*)dU, ld_du,
+                     tab, (int)M, (int)Rp, nsplit, accumulate, (int)db_blocks);
+  SLAM_CHECK_LAUNCH("slam_lora_bwd_sweep(finish)");
   return 0;
 }

@@ -78,9 +78,12 @@ SIGNATURES = {
     "slam_colsum_bf16": [P, I64, P, I64, I64, I32, P],
     "slam_skinny_gram_workspace_bytes": [I64, I64, I64],
     "slam_skinny_gram": [P, I64, P, I64, P, I64, I64, I64, I64, I64, F, I32, F, U64, U64, P, P],
+    "slam_lora_bwd_sweep_workspace_bytes": [I64, I64, I64, P, I64, I64],
+    "slam_lora_bwd_sweep": [P, I64, P, I64, P, I64, P, I64, I64, I64, I64, I64, P, I64, I32, I64, P, I64, P],
     "slam_lora_a_fwd": [P, I64, P, I64, P, I64, I64, I64, I64, I64, F, U64, U64, P],
     "slam_lora_hop_dropout": [P, I64, P, I64, P, I64, I64, I64, I64, F, U64, U64, P],
     "slam_lora_pack_b": [P, F, P, I64, P, I64, I64, I64, P],
+    "slam_lora_refresh": [P, I64, I64, P],
     "slam_gemm_skinny_workspace_bytes": [I64, I64, I64, I64, I32],
     "slam_gemm_skinny_bf16_nt": [P, I64, P, I64, P, I64, I64, P, I64, I64, I64, I64, P, I64, I32, I32, P, I64, I64, P],
     "slam_attn_decode": [P, I64, P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, I64,
@@ -103,6 +106,11 @@ SIGNATURES = {
     "slam_dropout_bf16": [P, I64, P, I64, I64, I64, F, ctypes.c_uint64, ctypes.c_uint64, I32, P],
     "slam_add_bf16": [P, I64, P, I64, I64, I64, P],
 }
+
+
+class LoraAdapter(ctypes.Structure):
+    """slam_lora_adapter of include/slam_hip.h (the adapter table of slam_lora_bwd_sweep)"""
+    _fields_ = [("row0", c_int64), ("rows", c_int64), ("j0", c_int64), ("r", c_int64), ("scale", c_float), ("dB", c_void_p)]
 
 
 class SlamHipError(RuntimeError):

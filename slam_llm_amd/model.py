@@ -61,6 +61,15 @@ FUSE_LORA_HOP = _os.environ.get("SLAM_FUSED_LORA_HOP", "1") == "1"
 # LoRA gradient products (dA / dB grams and their reduces) on a side stream under the next layer's GEMMs (round 6, VERDICT r5 next #5a):
 # bit-identical; SLAM_LORA_SIDE_STREAM=0 keeps them inline on the compute stream (A/B)
 LORA_SIDE_STREAM = _os.environ.get("SLAM_LORA_SIDE_STREAM", "0") == "1"
+# LoRA backward: du = dy . (sB) and every dB = s dy^T u of a fused group from ONE pass over dy (slam_lora_bwd_sweep) instead of the N = Rp
+# extension product + one gram (and reduce) per adapter, which read dy twice and the adapter-free parts once for nothing.  Same sums,
+# regrouped (fp32 accumulation, one bf16 rounding of du): not bit-identical.  SLAM_LORA_BWD_SWEEP=0 restores those launches (A/B).
+LORA_BWD_SWEEP = _os.environ.get("SLAM_LORA_BWD_SWEEP", "1") == "1"
+# Rows from which the sweep replaces them.  No batch was found at which the separate launches win: in the C1 step (380 rows, r 8) and the
+# C4 step (672 rows, r 32) the sweep measured neutral to slightly faster, launch for launch it ties or wins from 128 rows
+# (profiles/lora_bwd_sweep.md).  Below 256 rows (decode-sized batches) nothing was measured in a step and the launches stay as they were.
+# SLAM_LORA_BWD_SWEEP_MIN_M overrides (A/B).
+LORA_BWD_SWEEP_MIN_M = int(_os.environ.get("SLAM_LORA_BWD_SWEEP_MIN_M", "256"))
 _SIDE_STREAMS = {}
 
 
@@ -275,6 +284,14 @@ class FusedLinear:
         # their transpose [K, Rp] serves the second hop of the backward: dx += d(xA^T) . A
         self.AcatT = ops.transpose_into(getattr(self, "AcatT", None), self.a_cat(store), self.Rp)     # in place: see ops.transpose_into
 
+    def refresh_items(self, store: TrainableStore):
+        """what refresh() writes, as items of ops.lora_refresh_table (AcatT must exist): the batched refresh of a whole model"""
+        K = self.K
+        items = [("pack", store.master_view(a["B"]), a["scale"],
+                  self.Wext[a["row0"]: a["row0"] + a["rows"], K + a["j0"]: K + a["j0"] + a["r"]],
+                  self.WextT[K + a["j0"]: K + a["j0"] + a["r"], a["row0"]: a["row0"] + a["rows"]]) for a in self.adapters]
+        return items + [("transpose", self.a_cat(store), self.AcatT)]
+
     def a_cat(self, store: TrainableStore) -> torch.Tensor:
         first = self.adapters[0]
         off, _, _ = store.offsets[first["A"]]
@@ -284,6 +301,13 @@ class FusedLinear:
         first = self.adapters[0]
         off, _, _ = store.offsets[first["A"]]
         return store.grad[off: off + self.sum_r * self.K].view(self.sum_r, self.K)
+
+    def _sweep_table(self, store: TrainableStore):
+        """the adapter table of ops.lora_bwd_sweep (the lora_B gradient views of `store`), rebuilt when the gradient buffer moved"""
+        key = (id(store), store.grad.data_ptr())
+        if getattr(self, "_sweep_tab", (None, None))[0] != key:
+            self._sweep_tab = (key, ops.lora_adapter_table(self.adapters, [store.grad_view(a["B"]) for a in self.adapters]))
+        return self._sweep_tab[1]
 
     @property
     def hop_fills_pad(self) -> bool:
@@ -325,7 +349,18 @@ class FusedLinear:
                  accumulate: bool, out=None, drop=None, defer=None) -> torch.Tensor:
         """returns dx_ext [M, K+Rp] (columns [:K] are dL/dx); deposits adapter gradients into the store.
         defer(fn, keep): run the adapter-gradient products (off the dX critical path) through the caller's side queue instead of inline."""
-        if self.Rp and self.K % 256 == 0:
+        # one sweep over dy for du and every dB (see LORA_BWD_SWEEP).  Qualifies when the kernel's layout rules hold -- every adapter's row0
+        # and rows multiples of 64 (bands start 16-byte aligned and end inside the part), sum_r % 8 == 0 and Rp <= 64 (one K-extension
+        # granule) -- and the batch has LORA_BWD_SWEEP_MIN_M rows (see there); needs the forward's u (x_ext) and the store to deposit dB.
+        sweep = (LORA_BWD_SWEEP and bool(self.adapters) and x_ext is not None and store is not None and self.Rp <= 64
+                 and self.sum_r % 8 == 0 and all(a["row0"] % 64 == 0 and a["rows"] % 64 == 0 for a in self.adapters)
+                 and dy.shape[0] >= LORA_BWD_SWEEP_MIN_M)
+        if sweep:
+            K = self.K
+            dx_ext = out if out is not None else torch.empty((dy.shape[0], K + self.Rp), dtype=torch.bfloat16, device=dy.device)
+            ops.gemm_nt(dy, self.WextT[:K], out=dx_ext[:, :K])
+            ops.lora_bwd_sweep(dy, self.WextT[K:], x_ext[:, K:], dx_ext[:, K:], self._sweep_table(store), accumulate=accumulate)
+        elif self.Rp and self.K % 256 == 0:
             # two products instead of one [M, K + Rp] output: the Rp (64) extension columns would open a 17th column of 256-wide
             # tiles that is 25 % full -- at the Llama qkv shape 799 tiles = 3.12 rounds over 256 CUs, paid as 4 (measured 1.1 PF
             # vs 1.3 for its neighbours).  K columns = whole tiles, the extension = one narrow (N <= 64) product.
@@ -359,6 +394,8 @@ class FusedLinear:
                     if not merged:
                         ops.skinny_gram(dx_ext[:, K + a["j0"]: K + a["j0"] + r], xin, store.grad_view(a["A"]), K, 1,
                                         accumulate=accumulate, drop=drop)
+                    if sweep:
+                        continue                                          # dB came out of the sweep over dy
                     u = x_ext[:, K + a["j0"]: K + a["j0"] + r]            # xA^T        [M, r]
                     ops.skinny_gram(u, dy[:, a["row0"]: a["row0"] + a["rows"]], store.grad_view(a["B"]), 1, r,
                                     alpha=a["scale"], accumulate=accumulate)
@@ -2245,9 +2282,23 @@ class HipLlamaLora(nn.Module):
         return self
 
     def refresh(self):
-        for L in self.layers:
-            for fl in (L.qkv, L.o, L.gu, L.down):
-                fl.refresh(self.store)
+        """re-pack every adapter-derived operand (s B into [W | s B] and its transpose, A^T of each group) from the store: ONE launch walking
+        a device table instead of one lora_pack_b per adapter and one transpose per group (96 launches per Llama-3-8B step).  Destinations
+        are written in place (a captured step replays their addresses); the table holds raw addresses and is rebuilt when one of them moved."""
+        groups = [fl for L in self.layers for fl in (L.qkv, L.o, L.gu, L.down) if fl.adapters]
+        if not groups:
+            return
+        st = self.store
+        for fl in groups:
+            if getattr(fl, "AcatT", None) is None or tuple(fl.AcatT.shape) != (fl.K, fl.Rp):
+                fl.AcatT = torch.empty((fl.K, fl.Rp), dtype=torch.bfloat16, device=fl.device)
+        key = (st.flat.data_ptr(), st.flat_bf16.data_ptr()) + tuple(p for fl in groups for p in (fl.Wext.data_ptr(), fl.WextT.data_ptr(), fl.AcatT.data_ptr()))
+        if getattr(self, "_refresh_tab", (None,))[0] != key:
+            items = []
+            for fl in groups:
+                items += fl.refresh_items(st)
+            self._refresh_tab = (key,) + ops.lora_refresh_table(items, fl.device)
+        ops.lora_refresh(*self._refresh_tab[1:])
 
     def rope(self, T: int):
         if T not in self._rope:

@@ -892,6 +892,36 @@ def lora_pack_b(b_f32, scale, dst2d, dstT2d):
     call("slam_lora_pack_b", _p(b_f32), scale, _p(dst2d), _ld(dst2d), _p(dstT2d), _ld(dstT2d), rows, r, _s())
 
 
+def lora_refresh_table(items, device):
+    """device table of lora_refresh (include/slam_hip.h: slam_lora_refresh).  items: ("pack", B_f32 [rows, r], scale, dst2d, dstT2d) -- what
+    lora_pack_b takes -- or ("transpose", A_bf16 [sum_r, K], out [K, Rp]) -- what transpose(A, Rp, out) takes.  Returns (table, n_items,
+    n_blocks); the table holds raw addresses: the caller rebuilds it when any of these tensors is reallocated."""
+    import struct
+    rows_, blk = [], 0
+    for it in items:
+        if it[0] == "pack":
+            _, b, scale, dst, dstT = it
+            rows, r = b.shape
+            assert b.dtype == torch.float32 and b.is_contiguous() and tuple(dst.shape) == (rows, r) and tuple(dstT.shape) == (r, rows)
+            bits = struct.unpack("<i", struct.pack("<f", scale))[0]
+            rows_.append([0, rows, r, bits, b.data_ptr(), dst.data_ptr(), _ld(dst), dstT.data_ptr(), _ld(dstT), blk])
+            blk += min(256, (rows * r + 255) // 256)
+        else:
+            _, a, out = it
+            R, K = a.shape
+            Rp = out.shape[1]
+            assert a.dtype == torch.bfloat16 and a.is_contiguous() and out.dtype == torch.bfloat16 and out.shape[0] == K
+            assert K % 8 == 0 and Rp % 64 == 0 and Rp >= R and _ld(out) % 8 == 0
+            rows_.append([1, R, K, 0, a.data_ptr(), out.data_ptr(), _ld(out), 0, Rp, blk])
+            blk += (Rp // 64) * ((K + 63) // 64)
+    return torch.tensor(rows_, dtype=torch.int64).to(device), len(rows_), blk
+
+
+def lora_refresh(table, n_items, n_blocks):
+    """one launch for every item of a lora_refresh_table"""
+    call("slam_lora_refresh", _p(table), n_items, n_blocks, _s())
+
+
 def colsum(x2d, out_f32, accumulate=False):
     M, N = x2d.shape
     call("slam_colsum_bf16", _p(x2d), _ld(x2d), _p(out_f32), M, N, 1 if accumulate else 0, _s())
@@ -938,6 +968,40 @@ def skinny_gram(S2d, X2d, out, out_ld_r, out_ld_c, alpha=1.0, accumulate=False, 
     call("slam_skinny_gram", _p(S2d), _ld(S2d), _p(X2d), _ld(X2d), _p(out), out_ld_r, out_ld_c, M, R, C, alpha,
          1 if accumulate else 0, float(p_), int(seed) & (2 ** 64 - 1), int(off) & (2 ** 64 - 1), _p(_GRAM_WS[key]), _s())
     return out
+
+
+def lora_adapter_table(adapters, grads):
+    """the slam_lora_adapter table of lora_bwd_sweep: adapters = dicts with row0, rows, j0, r, scale; grads = their lora_B gradients
+    (fp32 [rows, r], contiguous; None for a workspace query only)"""
+    tab = (lib.LoraAdapter * len(adapters))()
+    for t, a, gr in zip(tab, adapters, grads):
+        if gr is not None:
+            assert gr.dtype == torch.float32 and gr.is_contiguous() and tuple(gr.shape) == (a["rows"], a["r"]) and gr.is_cuda
+        t.row0, t.rows, t.j0, t.r, t.scale = a["row0"], a["rows"], a["j0"], a["r"], a["scale"]
+        t.dB = gr.data_ptr() if gr is not None else None
+    return tab
+
+
+def lora_bwd_sweep(dy, bt, u, du, table, accumulate=False, splits=0):
+    """one pass over dy [M, N]: du[M, Rp] = dy @ bt[Rp, N]^T (bt = (s B)^T stacked, zero outside each adapter's columns; the padding
+    columns behind sum_r come out as zeros) and, for every adapter of `table` (lora_adapter_table), dB (+)= scale * dy[:, part]^T @ u[:, j0:j0+r].
+    Replaces gemm_nt(dy, bt) + one skinny_gram per adapter; fixed-order sums.  splits: row splits (0 = automatic)."""
+    M, N = dy.shape
+    Rp = du.shape[1]
+    sum_r = sum(t.r for t in table)
+    assert bt.shape == (Rp, N) and u.shape[0] == M and du.shape[0] == M and u.shape[1] >= sum_r
+    nbytes = call("slam_lora_bwd_sweep_workspace_bytes", M, N, sum_r, table, len(table), splits)
+    if nbytes < 0:
+        raise lib.SlamHipError(f"slam_lora_bwd_sweep_workspace_bytes failed: {lib.last_error()}")
+    key = f"sweep:{dy.device}:{torch.cuda.current_stream().cuda_stream}"    # per stream, grown to the largest need (as the gram workspace)
+    if key not in _GRAM_WS or _GRAM_WS[key].numel() * 4 < nbytes:
+        _GRAM_WS[key] = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dy.device)
+    ws = _GRAM_WS[key]
+    _timed("lora_bwd_sweep", 4.0 * M * sum(t.rows * t.r for t in table),
+           lambda: call("slam_lora_bwd_sweep", _p(dy), _ld(dy), _p(bt), _ld(bt), _p(u), _ld(u), _p(du), _ld(du), M, N, sum_r, Rp, table,
+                        len(table), 1 if accumulate else 0, splits, _p(ws), ws.numel() * 4, _s()),
+           nbytes=2.0 * M * sum(t.rows for t in table))
+    return du
 
 
 def cast_f32_(src_bf16, dst_f32, accumulate=False):
