@@ -145,9 +145,13 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ lo
       f[e] = bf2f(v[e]);
       if (f[e] > cm) { cm = f[e]; ci = e; }
     }
+    // a chunk of eight -inf logits (masked vocabulary entries) is the identity (m = -inf, s = 0): exp(-inf - -inf) would make its sum,
+    // and through ms_combine's s * 0 the whole row, NaN
     float cs = 0.f;
+    if (cm != -INFINITY) {
 #pragma unroll
-    for (int e = 0; e < 8; e++) cs += __expf(f[e] - cm);
+      for (int e = 0; e < 8; e++) cs += __expf(f[e] - cm);
+    }
     MaxSum b;
     b.m = cm; b.s = cs; b.idx = c * 8 + ci;
     a = ms_combine(a, b);

@@ -654,6 +654,7 @@ extern "C" int slam_layernorm_bwd(const void* x, int64_t ldx, const float* mean,
   SLAM_CHECK_ARG(x && mean && rstd && weight && dy, "slam_layernorm_bwd: null pointer");
   SLAM_CHECK_ARG(M > 0 && d > 0 && d % 8 == 0 && ldx % 8 == 0 && lddy % 8 == 0 && (!dx || lddx % 8 == 0), "slam_layernorm_bwd: bad shape");
   SLAM_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "slam_layernorm_bwd: dgamma/dbeta must both be set or both null");
+  SLAM_CHECK_ARG(ldx >= d && lddy >= d && (!dx || lddx >= d), "slam_layernorm_bwd: bad leading dims (ldx, lddy, lddx must be >= d)");
   hipStream_t s = (hipStream_t)stream;
   if (dx)
     hipLaunchKernelGGL(layernorm_bwd_dx_kernel, dim3((unsigned)cdiv64(M, ROWS_PER_BLOCK)), dim3(256), 0, s, (const bf16_t*)x, ldx,

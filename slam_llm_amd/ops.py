@@ -388,9 +388,9 @@ def layernorm(x, weight, bias, eps=1e-5, out=None, gelu=False, stats=False):
     return (out, mean, rstd) if stats else out
 
 
-def layernorm_bwd(x, mean, rstd, weight, dy, dgamma=None, dbeta=None, want_dx=True, accumulate=False):
+def layernorm_bwd(x, mean, rstd, weight, dy, dgamma=None, dbeta=None, want_dx=True, accumulate=False, out=None):
     M, d = x.shape
-    dx = torch.empty((M, d), dtype=torch.bfloat16, device=x.device) if want_dx else None
+    dx = (out if out is not None else torch.empty((M, d), dtype=torch.bfloat16, device=x.device)) if want_dx else None
     call("slam_layernorm_bwd", _p(x), _ld(x), _p(mean), _p(rstd), _p(weight), _p(dy), _ld(dy), _p(dx),
          _ld(dx) if dx is not None else 0, _p(dgamma), _p(dbeta), M, d, 1 if accumulate else 0, _s())
     return dx

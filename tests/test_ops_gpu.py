@@ -1675,3 +1675,440 @@ def test_attention_probability_dropout_fwd_bwd(dev, B, Tq, Tk, H, masked):
     o2, _ = ops.attn_fwd(qd, kvd[:, : H * D], vt, B, Tq, H, H, D, False, scale, key_mask=km.to(dev) if masked else None, Tk=Tk,
                          drop=(pdrop, seed + 1))
     assert not torch.equal(o2, o)
+
+
+# ----------------------------------------------------------------------------------------- row kernels against float64 (tests/rowwise_refs.py)
+# norm.hip, the elementwise kernels and the CE kernel: fp32 arithmetic from bf16 inputs, ONE rounding to bf16.  Every bound below is
+# 2^-8 |ref| plus the fp32 allowance DESIGN.md derives for that kernel (tests/test_rowwise_refs_host.py shows on the CPU that fp32
+# arithmetic in the kernel's order of additions needs less than a quarter of each allowance).  Inputs have a non-zero mean so a dropped
+# mean term shows; inputs and outputs are strided views into sentinel-filled buffers, so a store outside a row fails the test.
+from tests import rowwise_refs as R  # noqa: E402
+
+
+def rndm(shape, dev, seed, std=2.0, mean=0.5, dtype=torch.bfloat16):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * std + mean).to(dtype).to(dev)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and bool(torch.equal(_bits(a), _bits(b)))
+
+
+def _f32_out(n, dev):
+    return R.padded((n,), 8, dev, dtype=torch.float32)
+
+
+@pytest.mark.parametrize("M,d,gelu", [(5, 8, False), (37, 520, False), (9, 1536, False), (6, 4096, False), (7, 4104, False), (3, 8200, False),
+                                      (4096, 8, False), (4097, 1536, False), (37, 520, True), (7, 4104, True), (4097, 1536, True)])
+def test_layernorm_forward_y_mean_rstd_against_float64(dev, M, d, gelu):
+    """layernorm_kernel<true> (d <= 4096), <false> (d > 4096) and layernorm_narrow_kernel (M >= 4096, d <= 1536), each once with the GELU:
+    y within one rounding + 2^-20 (|w xhat| + |b|); mean within 2^-18 mean|x|, rstd within 2^-18 relative, both against float64"""
+    ops = _ops()
+    xc = rndm((M, d), dev, seed=101)
+    w, b = rnd((d,), dev, seed=102, dtype=torch.float32), rnd((d,), dev, seed=103, dtype=torch.float32)
+    x, y = R.padded_like(xc), R.padded((M, d), 8, dev)
+    _, mean, rstd = ops.layernorm(x, w, b, 1e-5, out=y, gelu=gelu, stats=True)
+    R.assert_padding_untouched(y, what="layernorm y")
+    R.assert_padding_untouched(x, what="layernorm x")
+    yc, mc, rc = ops.layernorm(xc, w, b, 1e-5, gelu=gelu, stats=True)
+    assert _same_bits(y, yc) and torch.equal(mean, mc) and torch.equal(rstd, rc), "strided and contiguous runs differ"
+    ry, rmean, rrstd = R.layernorm_ref(xc, w, b, 1e-5, gelu)
+    t = (R.f64(xc) - rmean[:, None]) * rrstd[:, None] * R.f64(w)
+    allow = 2.0 ** -20 * (t.abs() + R.f64(b).abs())
+    if gelu:    # |gelu'| <= 1.13 carries the pre-activation's allowance through; the GELU adds its own 2^-22 |t| (1 + erf cancels for t < -4)
+        allow = 1.13 * allow + 2.0 ** -22 * (t + R.f64(b)).abs()
+    R.assert_one_rounding(y, ry, allow, f"layernorm y{' +gelu' if gelu else ''}")
+    R.assert_within(mean, rmean, 2.0 ** -18 * R.f64(xc).abs().mean(-1), "layernorm mean")
+    R.assert_within(rstd, rrstd, 2.0 ** -18 * rrstd, "layernorm rstd")
+
+
+@pytest.mark.parametrize("M,d", [(1, 8), (31, 72), (37, 64), (130, 1288), (70, 5128), (4101, 1280)])
+def test_layernorm_backward_dx_dgamma_dbeta_against_float64(dev, M, d):
+    """layernorm_bwd_dx_kernel and layernorm_bwd_params_kernel (mean / rstd from the forward kernel): dx within one rounding +
+    2^-20 rstd max_row|dy w|, dgamma / dbeta within 2^-18 of the column's sum of |terms|.  Then the variants: no dx, no parameter
+    gradients, accumulation (bit-equal to prior + fresh) and x / dy as column slices of wider buffers."""
+    ops = _ops()
+    xc, dyc = rndm((M, d), dev, seed=111), rndm((M, d), dev, seed=112, std=1.0)
+    w = rnd((d,), dev, seed=113, dtype=torch.float32)
+    x, dy = R.padded_like(xc), R.padded_like(dyc)
+    _, mean, rstd = ops.layernorm(x, w, torch.zeros_like(w), 1e-5, stats=True)
+    dx, dg, db = R.padded((M, d), 8, dev), _f32_out(d, dev), _f32_out(d, dev)
+    ops.layernorm_bwd(x, mean, rstd, w, dy, dgamma=dg, dbeta=db, out=dx)
+    for t_, n_ in ((dx, "dx"), (dg, "dgamma"), (db, "dbeta")):
+        R.assert_padding_untouched(t_, what=f"layernorm_bwd {n_}")
+    rdx, rdg, rdb = R.layernorm_bwd_ref(xc, w, dyc)
+    _, rmean, rrstd = R.layernorm_ref(xc, w, torch.zeros_like(w), 1e-5)
+    gw = R.f64(dyc) * R.f64(w)
+    R.assert_one_rounding(dx, rdx, (2.0 ** -20 * rrstd * gw.abs().max(-1).values)[:, None], "layernorm_bwd dx")
+    xh = (R.f64(xc) - rmean[:, None]) * rrstd[:, None]
+    R.assert_within(dg, rdg, 2.0 ** -18 * (R.f64(dyc) * xh).abs().sum(0), "layernorm_bwd dgamma")
+    R.assert_within(db, rdb, 2.0 ** -18 * R.f64(dyc).abs().sum(0), "layernorm_bwd dbeta")
+    # parameter gradients only
+    dg2, db2 = _f32_out(d, dev), _f32_out(d, dev)
+    assert ops.layernorm_bwd(x, mean, rstd, w, dy, dgamma=dg2, dbeta=db2, want_dx=False) is None
+    assert _same_bits(dg2, dg) and _same_bits(db2, db)
+    R.assert_padding_untouched(dg2, what="dgamma (no dx)"), R.assert_padding_untouched(db2, what="dbeta (no dx)")
+    # dx only
+    assert _same_bits(ops.layernorm_bwd(x, mean, rstd, w, dy), dx)
+    # accumulation onto non-zero buffers
+    pg, pb = rnd((d,), dev, seed=114, dtype=torch.float32, std=3.0), rnd((d,), dev, seed=115, dtype=torch.float32, std=3.0)
+    ag, ab = _f32_out(d, dev), _f32_out(d, dev)
+    ag.copy_(pg), ab.copy_(pb)
+    ops.layernorm_bwd(x, mean, rstd, w, dy, dgamma=ag, dbeta=ab, want_dx=False, accumulate=True)
+    assert _same_bits(ag, pg + dg) and _same_bits(ab, pb + db), "accumulate is not prior + fresh"
+    R.assert_padding_untouched(ag, what="dgamma (accumulate)"), R.assert_padding_untouched(ab, what="dbeta (accumulate)")
+    # x and dy as column slices of wider buffers, the way the fused qkv / gate_up buffers are sliced
+    wx, wdy = R.padded((M, d + 16), 8, dev), R.padded((M, d + 16), 8, dev)
+    wx[:, 8:8 + d].copy_(xc), wdy[:, 8:8 + d].copy_(dyc)
+    dg3, db3 = _f32_out(d, dev), _f32_out(d, dev)
+    dx3 = ops.layernorm_bwd(wx[:, 8:8 + d], mean, rstd, w, wdy[:, 8:8 + d], dgamma=dg3, dbeta=db3)
+    assert _same_bits(dx3, dx) and _same_bits(dg3, dg) and _same_bits(db3, db), "column-sliced operands give other bits"
+
+
+def test_layernorm_bwd_rejects_rows_narrower_than_d(dev):
+    ops = _ops()
+    from slam_llm_amd.lib import SlamHipError
+    M, d = 4, 64
+    x, dy, w = rnd((M, d), dev, seed=1), rnd((M, d), dev, seed=2), rnd((d,), dev, seed=3, dtype=torch.float32)
+    mean, rstd = torch.zeros(M, device=dev), torch.ones(M, device=dev)
+    narrow = torch.as_strided(x, (M, d), (d - 8, 1))        # row pitch d - 8 < d: rows overlap
+    with pytest.raises(SlamHipError, match="slam_layernorm_bwd: bad leading dims"):
+        ops.layernorm_bwd(narrow, mean, rstd, w, dy)
+    with pytest.raises(SlamHipError, match="slam_layernorm_bwd: bad leading dims"):
+        ops.layernorm_bwd(x, mean, rstd, w, torch.as_strided(dy, (M, d), (d - 8, 1)))
+    with pytest.raises(SlamHipError, match="slam_layernorm_bwd: bad leading dims"):
+        ops.layernorm_bwd(x, mean, rstd, w, dy, out=torch.as_strided(torch.empty_like(x), (M, d), (d - 8, 1)))
+
+
+@pytest.mark.parametrize("M,d", [(1, 8), (128, 896), (129, 896), (3, 8192), (2, 8200), (130, 3584), (130, 4104), (130, 5120)])
+def test_rmsnorm_forward_y_rstd_against_float64(dev, M, d):
+    """rmsnorm_fwd_small_kernel (M <= 128 and d <= 8192), rmsnorm_fwd_kernel<true> (d <= 4096) and <false>; widths whose last round of
+    16-byte chunks is partial (896 = 112 chunks, 3584 = 448).  Two roundings (HF: w * bf16(x rstd)); the reference does the inner one, so
+    a result differs from one rounding of the reference only where the fp32 and the float64 x * rstd fall on two sides of a bf16 tie:
+    nothing beyond (2^-8 + 2^-7)|ref|, at most 0.1 % of the elements beyond 2^-8 |ref| (fp32 allowance 2^-20 |ref| in both)."""
+    ops = _ops()
+    xc = rndm((M, d), dev, seed=121)
+    w = (1 + 0.1 * torch.randn(d, generator=torch.Generator().manual_seed(122))).to(dev)
+    x, y = R.padded_like(xc), R.padded((M, d), 8, dev)
+    _, rstd = ops.rmsnorm_fwd(x, w, 1e-5, out=y)
+    R.assert_padding_untouched(y, what="rmsnorm y")
+    yc, rc = ops.rmsnorm_fwd(xc, w, 1e-5)
+    assert _same_bits(y, yc) and torch.equal(rstd, rc), "strided and contiguous runs differ"
+    ry, rrstd = R.rmsnorm_ref(xc, w, 1e-5)
+    R.assert_within(rstd, rrstd, 2.0 ** -18 * rrstd, "rmsnorm rstd")
+    allow = 2.0 ** -20 * ry.abs()
+    R.assert_within(y, ry, (R.U_BF16 + 2.0 ** -7) * ry.abs() + allow, "rmsnorm y (two roundings)")
+    beyond = int((R.excess_over_one_rounding(y, ry) > allow).sum())
+    print(f"ROWWISE-SHARE\trmsnorm y: elements beyond one rounding\t{beyond / (M * d):.2e}")
+    assert beyond <= 1e-3 * M * d, f"{beyond} of {M * d} elements beyond one rounding"
+
+
+@pytest.mark.parametrize("variant", ["dres+scale", "dres", "scale", "neither"])
+@pytest.mark.parametrize("M,d", [(1, 8), (5, 896), (130, 3584), (130, 4104)])
+def test_rmsnorm_backward_against_float64(dev, M, d, variant):
+    """rmsnorm_bwd_kernel<true> / <false> with and without the residual gradient and the gradient scale (without dres its registers are
+    never loaded): one rounding + 2^-20 scale rstd max_row|dy w|, plus one more 2^-8 |dres| where dres is added"""
+    ops = _ops()
+    xc, dyc, drc = rndm((M, d), dev, seed=131), rndm((M, d), dev, seed=132, std=1.0), rndm((M, d), dev, seed=133, std=1.0)
+    w = (1 + 0.1 * torch.randn(d, generator=torch.Generator().manual_seed(134))).to(dev)
+    x, dy = R.padded_like(xc), R.padded_like(dyc)
+    dres = R.padded_like(drc) if "dres" in variant else None
+    scale = torch.tensor([0.5], device=dev) if "scale" in variant else None
+    _, rstd = ops.rmsnorm_fwd(x, w, 1e-5)
+    dx = R.padded((M, d), 8, dev)
+    ops.rmsnorm_bwd(x, rstd, w, dy, dres=dres, grad_scale=scale, out=dx)
+    R.assert_padding_untouched(dx, what="rmsnorm_bwd dx")
+    s = 0.5 if scale is not None else None
+    ref = R.rmsnorm_bwd_ref(xc, w, dyc, drc if dres is not None else None, s, eps=1e-5)
+    _, rrstd = R.rmsnorm_ref(xc, w, 1e-5)
+    allow = (2.0 ** -20 * (s or 1.0) * rrstd * (R.f64(dyc) * R.f64(w)).abs().max(-1).values)[:, None]
+    if dres is not None:
+        allow = allow + R.U_BF16 * R.f64(drc).abs()
+    R.assert_one_rounding(dx, ref, allow, f"rmsnorm_bwd dx ({variant})")
+
+
+def test_gelu_forward_over_every_bf16_value(dev):
+    """gelu_fwd_kernel on every finite bf16 with 2^-40 <= |x| <= 2^40 and on +-0: one rounding + 2^-22 |x| (1 + erf cancels for x < -4)"""
+    ops = _ops()
+    xc = R.sweep_matrix(dev)
+    x, y = R.padded_like(xc), R.padded(tuple(xc.shape), 8, dev)
+    ops.gelu_fwd(x, out=y)
+    R.assert_padding_untouched(y, what="gelu_fwd")
+    assert _same_bits(y, ops.gelu_fwd(xc))
+    R.assert_one_rounding(y, R.gelu_ref(xc), 2.0 ** -22 * R.f64(xc).abs(), "gelu_fwd sweep")
+
+
+GELU_BWD_ALLOWANCE = 2.0 ** -20     # x |dy|, beyond one rounding
+
+
+@pytest.mark.parametrize("dy_kind", ["ones", "random"])
+def test_gelu_backward_over_every_bf16_value(dev, dy_kind):
+    """gelu_bwd_kernel (its pdf uses the hardware exponential, __expf) over the same sweep, dy = 1 and a random dy:
+    one rounding + 2^-20 |dy|.  Measured on an MI355X: the worst absolute excess over one rounding is 1.27e-8 |dy| (dy = 1: 1.24e-8), at
+    x = -5.5625 -- below the 2.3e-8 an accurate exponential needs on the CPU and 75 times below 2^-20, so the allowance stays 2^-20."""
+    ops = _ops()
+    xc = R.sweep_matrix(dev)
+    dyc = torch.ones_like(xc) if dy_kind == "ones" else rnd(tuple(xc.shape), dev, seed=141)
+    x, dy, dz = R.padded_like(xc), R.padded_like(dyc), R.padded(tuple(xc.shape), 8, dev)
+    ops.gelu_bwd(x, dy, out=dz)
+    R.assert_padding_untouched(dz, what="gelu_bwd")
+    ref = R.gelu_bwd_ref(xc, dyc)
+    ex = R.excess_over_one_rounding(dz, ref) / R.f64(dyc).abs().clamp(min=2.0 ** -126)
+    i = int(ex.argmax())
+    print(f"ROWWISE-EXCESS\tgelu_bwd ({dy_kind})\tworst excess over one rounding {float(ex.flatten()[i]):.3e} x |dy| at x = {float(xc.flatten()[i])!r}")
+    R.assert_one_rounding(dz, ref, GELU_BWD_ALLOWANCE * R.f64(dyc).abs(), f"gelu_bwd sweep (dy {dy_kind})")
+
+
+def test_relu_backward_is_bit_exact_over_every_bf16_value(dev):
+    """relu_bwd_kernel in place on a strided dh: dh's bits are kept where h > 0 and become +0 elsewhere (h = -0 and h = +0 included)"""
+    ops = _ops()
+    hc = R.sweep_matrix(dev)
+    dhc = rnd(tuple(hc.shape), dev, seed=151)
+    h, dh = R.padded_like(hc), R.padded_like(dhc)
+    ops.relu_bwd_(dh, h)
+    R.assert_padding_untouched(dh, what="relu_bwd_")
+    want = torch.where(hc.float() > 0, _bits(dhc), torch.zeros_like(_bits(dhc)))
+    assert torch.equal(_bits(dh), want)
+    assert int((hc.float() > 0).sum()) == 10241 and int((hc.float() == 0).sum()) >= 2
+
+
+@pytest.mark.parametrize("up", [1.0, -0.75, 3.0])
+def test_swiglu_forward_backward_over_every_bf16_gate(dev, up):
+    """swiglu_fwd_kernel / swiglu_bwd_kernel<false> with the gate swept over every bf16 value.  Their logistic is rcp(1 + exp2(-g log2 e))
+    on the hardware units: the fp32 product g log2(e) carries |g| 2^-24 into the exponent, at most 2^-17.4 relative for the |g| < 88 at which
+    the logistic is not yet flushed, and a logistic below 2^-126 is flushed to 0 (|g sigma(g)| < 88 x 2^-126 < 2^-119 there).  So:
+    h and dup within one rounding + 2^-16 |ref| + 2^-119 |u| (|dh|); dgate = dh u s (1 + g (1 - s)) has a zero near g = -1.28, its factor is
+    bounded by 1.1 and its fp32 error by 20 x 2^-24 (g (1 - s) for g <= 17.3, where 1 - s leaves fp32): one rounding + 2^-18 |dh u|."""
+    ops = _ops()
+    g = R.sweep_matrix(dev)
+    M, Fd = g.shape
+    guc = torch.cat([g, torch.full_like(g, up)], dim=1)
+    dhc = rnd((M, Fd), dev, seed=161)
+    gu, dh = R.padded_like(guc), R.padded_like(dhc)
+    h, dgu = R.padded((M, Fd), 8, dev), R.padded((M, 2 * Fd), 8, dev)
+    ops.swiglu_fwd(gu, out=h)
+    ops.swiglu_bwd(gu, dh, out=dgu)
+    R.assert_padding_untouched(h, what="swiglu_fwd"), R.assert_padding_untouched(dgu, what="swiglu_bwd")
+    g64, d64 = R.f64(g), R.f64(dhc)
+    s = 1.0 / (1.0 + torch.exp(-g64))
+    silu = g64 * s
+    R.assert_one_rounding(h, silu * up, 2.0 ** -16 * (silu * up).abs() + 2.0 ** -119 * abs(up), f"swiglu_fwd sweep (up {up})")
+    rdu = d64 * silu
+    R.assert_one_rounding(dgu[:, Fd:], rdu, 2.0 ** -16 * rdu.abs() + 2.0 ** -119 * d64.abs(), f"swiglu_bwd dup sweep (up {up})")
+    R.assert_one_rounding(dgu[:, :Fd], d64 * up * s * (1.0 + g64 * (1.0 - s)), 2.0 ** -18 * (d64 * up).abs(), f"swiglu_bwd dgate sweep (up {up})")
+
+
+def test_add_and_casts_are_bit_exact(dev):
+    """add_bf16_kernel, cast_f32_bf16_kernel, cast_bf16_f32_kernel against torch, bit for bit; the fp32 -> bf16 inputs hold exact ties under
+    even and odd upper halves, their neighbours, +-inf and NaN"""
+    ops = _ops()
+    ac, bc = rndm((37, 520), dev, seed=171), rndm((37, 520), dev, seed=172, std=1.0)
+    a, b = R.padded_like(ac), R.padded_like(bc)
+    ops.add_(a, b)
+    R.assert_padding_untouched(a, what="add_")
+    assert _same_bits(a, (ac.float() + bc.float()).bfloat16()) and _same_bits(b, bc)
+    n = 10007
+    gen = torch.Generator().manual_seed(173)
+    hi = torch.randint(0x0080, 0x7F80, (n,), generator=gen, dtype=torch.int32)               # finite normal upper halves, even and odd (no fp32 subnormals, as in bf16_sweep)
+    lo = torch.tensor([0x8000, 0x7FFF, 0x8001, 0x0000, 0xFFFF, 0x0001], dtype=torch.int32)[torch.arange(n) % 6]
+    lo[6000:] = torch.randint(0, 0x10000, (n - 6000,), generator=gen, dtype=torch.int32)
+    bits = (hi << 16) | lo
+    bits[1::2] |= -0x80000000                                                                # every other one negative
+    src = bits.view(torch.float32).clone()
+    src[:3] = torch.tensor([float("inf"), float("-inf"), float("nan")])
+    assert int(((bits & 0xFFFF) == 0x8000).sum()) > 500 and int((((bits >> 16) & 1) == 1).sum()) > 1000
+    src = src.to(dev)
+    out = R.padded((n,), 8, dev)
+    ops.cast_bf16(src, out)
+    R.assert_padding_untouched(out, what="cast_bf16")
+    assert _same_bits(out, src.to(torch.bfloat16))
+    sb = rndm((n,), dev, seed=174)
+    f = _f32_out(n, dev)
+    ops.cast_f32_(sb, f)
+    assert _same_bits(f, sb.float())
+    prior = rnd((n,), dev, seed=175, dtype=torch.float32, std=3.0)
+    f.copy_(prior)
+    ops.cast_f32_(sb, f, accumulate=True)
+    assert _same_bits(f, prior + sb.float())
+    R.assert_padding_untouched(f, what="cast_f32_")
+
+
+@pytest.mark.parametrize("op", ["gelu_fwd", "gelu_bwd", "add_", "relu_bwd_", "dropout", "swiglu_fwd", "swiglu_bwd", "cast_bf16", "cast_f32_"])
+def test_elementwise_second_trip_of_the_grid_stride_loop(dev, op):
+    """the elementwise launches cap their grid at 16384 workgroups of 256 threads and stride over the rest: 4100 x 8192 is 4 198 400
+    16-byte chunks, 4096 more than one trip.  The whole tensor in one launch must equal the same op over rows [0, 4096) and [4096, 4100),
+    each a single trip (whose arithmetic the sweeps above check); compared on the device.  The casts: n = 4 194 304 + 1001 against torch."""
+    ops = _ops()
+    M, N, cut = 4100, 8192, 4096
+    g = torch.Generator(device=dev).manual_seed(181)
+
+    def dr(*shape):
+        return (torch.randn(*shape, device=dev, generator=g) * 2.0 + 0.5).bfloat16()
+    if op in ("cast_bf16", "cast_f32_"):
+        n = 4194304 + 1001
+        if op == "cast_bf16":
+            src = torch.randn(n, device=dev, generator=g)
+            out = R.padded((n,), 8, dev)
+            ops.cast_bf16(src, out)
+            assert _same_bits(out, src.to(torch.bfloat16))
+        else:
+            src, out = dr(n), _f32_out(n, dev)
+            ops.cast_f32_(src, out)
+            assert _same_bits(out, src.float())
+        R.assert_padding_untouched(out, what=op)
+        return
+    x = dr(M, N)
+    if op == "gelu_fwd":
+        run = lambda r: ops.gelu_fwd(x[r])                                                    # noqa: E731
+    elif op == "gelu_bwd":
+        dy = dr(M, N)
+        run = lambda r: ops.gelu_bwd(x[r], dy[r])                                             # noqa: E731
+    elif op == "add_":
+        b = dr(M, N)
+        run = lambda r: ops.add_(x[r].clone(), b[r])                                          # noqa: E731
+    elif op == "relu_bwd_":
+        h = dr(M, N)
+        run = lambda r: ops.relu_bwd_(x[r].clone(), h[r])                                     # noqa: E731
+    elif op == "swiglu_fwd":
+        gu = torch.cat([x, dr(M, N)], dim=1)
+        run = lambda r: ops.swiglu_fwd(gu[r])                                                 # noqa: E731
+    elif op == "swiglu_bwd":
+        gu, dh = torch.cat([x, dr(M, N)], dim=1), dr(M, N)
+        run = lambda r: ops.swiglu_bwd(gu[r], dh[r])                                          # noqa: E731
+    else:
+        p, seed, off = 0.25, 2 ** 63 + 99, (7 << 40) + 8
+        ones = torch.ones((M, N), dtype=torch.bfloat16, device=dev)
+        mask = ops.dropout(ones, p, seed=seed, offset=off)
+        idx = np.uint64(off) + np.uint64((M - 8) * N) + np.arange(8 * N, dtype=np.uint64)     # the host hash for the last 8 rows only
+        z = G.mix64(seed, idx >> np.uint64(2))
+        bits = (z >> (np.uint64(16) * (idx & np.uint64(3)))) & np.uint64(0xFFFF)
+        host = torch.from_numpy((bits >= np.uint64(min(65535, int(p * 65536.0 + 0.5)))).reshape(8, N))
+        assert torch.equal(mask[M - 8:].float().cpu().ne(0), host)
+        run = lambda r: ops.dropout(x[r], p, seed=seed, offset=off + r.start * N)             # noqa: E731
+    whole = run(slice(0, M))
+    assert bool(torch.equal(_bits(whole[:cut]), _bits(run(slice(0, cut))))), f"{op}: first trip differs"
+    assert bool(torch.equal(_bits(whole[cut:]), _bits(run(slice(cut, M))))), f"{op}: second trip differs"
+    assert bool(whole[cut:].float().abs().sum() > 0)
+
+
+@pytest.mark.parametrize("M,N", [(1, 8), (31, 72), (33, 64), (1000, 520), (4101, 1288)])
+def test_colsum_against_float64(dev, M, N):
+    """colsum_kernel on its own: within 2^-18 of the column's sum of |x|; a column tail (N % 64 != 0), fewer rows than the 32 row
+    strides, the slice x[:, 8:8+N] of a wider buffer (the way model.py calls it), and accumulate = prior + fresh bit for bit"""
+    ops = _ops()
+    xc = rndm((M, N), dev, seed=191)
+    wide = R.padded((M, N + 16), 8, dev)
+    wide[:, 8:8 + N].copy_(xc)
+    out, out2 = _f32_out(N, dev), _f32_out(N, dev)
+    ops.colsum(R.padded_like(xc), out)
+    ops.colsum(wide[:, 8:8 + N], out2)
+    R.assert_padding_untouched(out, what="colsum"), R.assert_padding_untouched(out2, what="colsum (slice)")
+    R.assert_within(out, R.colsum_ref(xc), 2.0 ** -18 * R.f64(xc).abs().sum(0), "colsum")
+    assert _same_bits(out2, out)
+    prior = rnd((N,), dev, seed=192, dtype=torch.float32, std=3.0)
+    acc = _f32_out(N, dev)
+    acc.copy_(prior)
+    ops.colsum(xc, acc, accumulate=True)
+    assert _same_bits(acc, prior + out)
+    R.assert_padding_untouched(acc, what="colsum (accumulate)")
+
+
+def _ce_run(ops, logits, targets, write_grad=True):
+    dev_ = logits.device
+    tgt = targets.to(torch.int32).to(dev_)
+    nv = (tgt >= 0).sum().to(torch.int32).reshape(1)
+    rows = logits.shape[0]
+    row_loss = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev_)
+    row_ok = torch.full((rows,), -7, dtype=torch.int32, device=dev_)
+    ops.ce_fwd_bwd(logits, tgt, nv, row_loss, row_ok, write_grad=write_grad)
+    return row_loss, row_ok, nv
+
+
+def _ce_check(ops, lc, targets, what, pad):
+    """lc: contiguous bf16 logits (kept); runs the kernel on a copy (row pitch V + pad) and checks loss, gradient, argmax and the mean"""
+    lg = R.padded_like(lc, pad) if pad else lc.clone()
+    row_loss, row_ok, nv = _ce_run(ops, lg, targets)
+    if pad:
+        R.assert_padding_untouched(lg, what=f"{what}: dlogits")
+    loss, dl, am, mean = R.ce_ref(lc, targets)
+    assert torch.isfinite(loss).all() and (torch.isfinite(mean) or int(nv) == 0)
+    R.assert_within(row_loss, loss, 1e-4 * loss.abs().clamp(min=1.0), f"{what}: row loss")
+    assert bool(torch.isfinite(lg.float()).all()), f"{what}: non-finite gradient"
+    assert_close(lg, dl, atol=2e-5, rtol=1.5e-2, what=f"{what}: dlogits")
+    valid = targets >= 0
+    assert torch.equal(row_ok.cpu().long(), ((am == targets) & valid).long()), f"{what}: row_correct"
+    assert bool((lg[~valid.to(lg.device)] == 0).all()) and int(nv) == int(valid.sum())
+    out = ops.ce_finalize(row_loss, row_ok, nv).cpu()
+    if int(nv):
+        assert abs(float(out[0]) - float(mean)) <= 1e-4 * max(1.0, abs(float(mean))), f"{what}: mean loss"
+        assert abs(float(out[1]) - float(((am == targets) & valid).sum()) / int(nv)) < 1e-6
+    # write_grad = False: logits bit-unchanged, same row losses
+    lg2 = R.padded_like(lc, pad) if pad else lc.clone()
+    row_loss2, row_ok2, _ = _ce_run(ops, lg2, targets, write_grad=False)
+    assert _same_bits(lg2, lc) and _same_bits(row_loss2, row_loss) and torch.equal(row_ok2, row_ok), f"{what}: write_grad=False"
+    return row_loss, row_ok, nv, lg
+
+
+@pytest.mark.parametrize("pad", [0, 8])
+@pytest.mark.parametrize("V", [8, 2056, 128256, 151936])
+def test_cross_entropy_rows_against_float64(dev, V, pad):
+    """ce_fwd_bwd_kernel at one chunk per row (V = 8), at 257 chunks (thread 0 alone takes two) and at the Llama-3 / Qwen2 vocabularies; rows of
+    pitch V and V + 8 (the padding must survive both the gradient write of a labelled row and the zeroing of an ignored one); the last row is ignored"""
+    ops = _ops()
+    rows = 5 if V <= 2056 else 4
+    lc = rnd((rows, V), dev, seed=201, std=2.0)
+    t = torch.randint(0, V, (rows,), generator=torch.Generator().manual_seed(202))
+    t[0] = int(lc[0].float().argmax())          # one row whose prediction is right
+    t[-1] = -1
+    _, row_ok, _, _ = _ce_check(ops, lc, t, f"ce V={V} ld=V+{pad}", pad)
+    assert int(row_ok[0]) == 1
+
+
+@pytest.mark.parametrize("V", [2056, 128256])
+def test_cross_entropy_argmax_ties_take_the_first_index(dev, V):
+    """the row maximum sits at columns 5 (thread 0, first chunk), 2049 (thread 0 again, one trip later) and V - 1 (another wave): the
+    prediction is column 5, as torch.argmax's first index, so only the row whose target is 5 counts as correct"""
+    ops = _ops()
+    lc = rnd((4, V), dev, seed=211, std=2.0).clamp(max=9.0)
+    lc[:, 5] = lc[:, 2049] = lc[:, V - 1] = 10.0
+    t = torch.tensor([5, 2049, V - 1, -1])
+    _, row_ok, _, _ = _ce_check(ops, lc, t, f"ce ties V={V}", 8)
+    assert row_ok.cpu().tolist() == [1, 0, 0, 0]
+
+
+def test_cross_entropy_extreme_logits_and_all_rows_ignored(dev):
+    ops = _ops()
+    V = 2056
+    lc = (rnd((5, V), dev, seed=221, std=40.0)).clamp(-88.0, 88.0)
+    lc[0, 7], lc[1, 9] = 88.0, -88.0
+    t = torch.tensor([7, 9, 100, 2055, -1])         # a target at the top (loss ~ 0) and one at the bottom (loss ~ 176)
+    row_loss, _, _, _ = _ce_check(ops, lc, t, "ce logits up to +-88", 8)
+    assert bool(torch.isfinite(row_loss).all()) and float(row_loss[1]) > 100.0
+    # no labelled row at all: every gradient row zero, n_valid 0, and the mean over an empty selection is NaN (as torch's; ce_finalize_kernel says so)
+    row_loss, row_ok, nv, lg = _ce_check(ops, lc, torch.full((5,), -1), "ce all ignored", 8)
+    assert int(nv) == 0 and bool((lg == 0).all()) and bool((row_loss == 0).all()) and bool((row_ok == 0).all())
+    assert bool(torch.isnan(ops.ce_finalize(row_loss, row_ok, nv)).all())
+
+
+@pytest.mark.parametrize("V", [264, 2056])
+def test_cross_entropy_rows_with_minus_inf_logits(dev, V):
+    """masked vocabulary entries: one aligned group of eight -inf (a whole 16-byte chunk), a chunk that is -inf in part, and a row that
+    is -inf everywhere but the target and two more columns.  torch gives a finite loss; so must the kernel, with gradient 0 at -inf"""
+    ops = _ops()
+    lc = rnd((5, V), dev, seed=231, std=2.0)
+    lc[0, 16:24] = float("-inf")
+    lc[1, 0:8] = float("-inf")                   # the first chunk thread 0 sees
+    lc[1, V - 5:] = float("-inf")
+    keep = lc[2, [3, 130, V - 1]].clone()
+    lc[2] = float("-inf")
+    lc[2, [3, 130, V - 1]] = keep
+    lc[3, 40:48] = float("-inf")
+    lc[3, 41] = 1.0                              # a chunk with one finite logit among -inf
+    t = torch.tensor([30, 9, 130, 41, -1])
+    row_loss, _, _, lg = _ce_check(ops, lc, t, f"ce -inf V={V}", 8)
+    assert bool(torch.isfinite(row_loss).all()) and bool(torch.isfinite(lg.float()).all())
+    assert bool((lg[0, 16:24] == 0).all()) and bool((lg[2, :3] == 0).all())
