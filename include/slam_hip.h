@@ -90,6 +90,12 @@ int slam_gemm_set_workspace(void* workspace, int64_t bytes);
 int slam_gemm_set_group_m(int group_m);   /* tuning knob: M-tiles per raster group of the 256x256 kernels; 0 (default) = the per-shape rule, 1..64 forced */
 int slam_gemm_set_group_m_rule(int short_k_many_cols, int long_k_narrow, int wide_k4096, int other);   /* tools: the per-shape rule's four values (defaults 12, 4, 4, 8) */
 int slam_gemm_set_config(int cfg);   /* also: 100+v / 200+v = the 256x256 kernel of the auto rule for K > 2048 / <= 2048; 300 / 301 / 302..316 = split-K tail auto / off / forced slices; 400 / 401 = cycle stamps off / on (tools) */
+int slam_gemm_get_config(void);   /* returns (not a status) the forced kernel as slam_gemm_set_config left it: 0 = auto rule | 1 2 3 4 6 7 11 12 */
+/* which kernel slam_gemm_bf16_nt runs this product on under the current knobs and workspace (act 0..3), or slam_gemm_swiglu_bf16_nt
+ * (act 4): its label, NUL-terminated, into out[out_bytes] (64 bytes hold every label) -- the template instance's name,
+ * "gemm_ts_kernel", or "gemm_nt_w4_kernel<256,256,false,0> split-K x<S> + reduce" for the mid-M two-launch plan.  The same function
+ * decides the launch, so per-kernel timers and profiles that key on the label cannot drift from it.  Launches nothing. */
+int slam_gemm_kernel_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int act, char* out, int64_t out_bytes);
 /* tools only (after slam_gemm_set_config(401): production launches never write the stamps): {shader cycles, 100 MHz ticks} at
  * entry and exit of workgroup 0 of the last pipelined-kernel launch (synchronise first); effective shader clock of the launch = d(cycles) / d(ticks) x 100 MHz -- how the DVFS cost of a variant is read */
 int slam_gemm_debug_clock(unsigned long long* out6);   /* [4] = cycles at the k-loop's start, [5] = after the epilogue */

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "gemm_common.h"
 #include <atomic>
+#include <cstdio>
 #include <type_traits>
 
 namespace {
@@ -934,11 +935,8 @@ __global__ __launch_bounds__(256) void gemm_ts_reduce_kernel(GemmParams p, TsPla
 
 std::atomic<int> g_gemm_ts{1};   // 1 = N <= 64 products take the tall-skinny K-sliced kernel (DEFAULT), 0 = the 128 x 64 tile kernel (A/B)
 
-// -> true when launched
-static bool launch_gemm_ts(GemmParams& p, hipStream_t stream, int* rc) {
-  // (large M: the staged 128 x 64 tile kernel streams A in full 128-byte lines and wins -- 56 vs 96 us at 11780 x 64 x 6144; this
-  // kernel's fragment-shaped loads are 64-byte row segments.  It is the form for FEW rows and a long K: 102 -> 37 us at 672 x 64 x 12288)
-  if (!g_gemm_ts || p.N > 64 || p.M > 4096 || p.act == 3 || p.act == 4 || p.K < 256) return false;
+// (gemm_plan decides which products come here)
+static int launch_gemm_ts(GemmParams& p, hipStream_t stream) {
   const int rb = (p.M + 63) / 64;
   const int nk = p.K / 32;
   int S = 1024 / rb;
@@ -954,14 +952,8 @@ static bool launch_gemm_ts(GemmParams& p, hipStream_t stream, int* rc) {
   TsPlan pl{S, nk, ws};
   hipLaunchKernelGGL(gemm_ts_kernel, dim3((unsigned)rb, (unsigned)S), dim3(256), 0, stream, p, pl);
   if (S > 1) hipLaunchKernelGGL(gemm_ts_reduce_kernel, dim3((unsigned)((p.M + 15) / 16)), dim3(64), 0, stream, p, pl);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    slam_set_error("slam_gemm_bf16_nt(tall-skinny): launch failed: %s", hipGetErrorString(e));
-    *rc = -2;
-  } else {
-    *rc = 0;
-  }
-  return true;
+  SLAM_CHECK_LAUNCH("slam_gemm_bf16_nt(tall-skinny)");
+  return 0;
 }
 
 template <int BM, int BN, bool REG, int ABL, bool PROBE, int SK>
@@ -1200,6 +1192,92 @@ extern "C" int slam_gemm_set_config(int cfg) {
   return 0;
 }
 
+extern "C" int slam_gemm_get_config() { return g_gemm_cfg; }   // the forced kernel (0 = auto rule) as slam_gemm_set_config(0 | 1 2 3 4 6 7 11 12) left it
+
+// ---- which kernel a product runs on: the ONE place that decides (slam_gemm_bf16_nt dispatches on it, slam_gemm_swiglu_supported and
+// slam_gemm_kernel_name ask it) ------------------------------------------------------------------------------------------------------
+constexpr int GEMM_TS = 64;   // GemmPlan::kernel of the tall-skinny kernel (the others are the slam_gemm_set_config numbers)
+struct GemmPlan {
+  int kernel;              // 1 2 3 4 6 7 11 12 | GEMM_TS
+  int two_launch_slices;   // >= 2: the mid-M plan (kernel 12 on that many K slices + the reduce launch), else 0
+};
+
+static const char* gemm_kernel_label(int kernel) {   // (bench.py and profiles/pmc.json match on these strings)
+  switch (kernel) {
+    case 1: return "gemm_nt_kernel<128,128,2,2>";
+    case 11: return "gemm_nt_pipe_kernel<128,128,2,2,1>";
+    case 2: return "gemm_nt_kernel<256,128,4,2>";
+    case 3: return "gemm_nt_kernel<128,64,2,2>";
+    case 4: return "gemm_nt_kernel<256,256,2,4>";
+    case 6: return "gemm_nt_pipe_kernel<256,256,2,4,1>";
+    case 7: return "gemm_nt_persist2_kernel<256,256,2,4>";
+    case 12: return "gemm_nt_w4_kernel<256,256,false,0>";
+    case GEMM_TS: return "gemm_ts_kernel";
+  }
+  return nullptr;
+}
+
+// act: slam_gemm_bf16_nt's 0..3, or 4 for slam_gemm_swiglu_bf16_nt.  That entry point launches the 4-wave kernel itself, in one launch
+// and behind its own operand-extent test, so for act 4 neither the mid-M plan nor the descriptor fall-back of kernel 12 applies.
+static GemmPlan gemm_plan(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int act) {
+  int kernel = g_gemm_cfg;
+  // N <= 64, FEW rows and a long K: the tall-skinny K-sliced kernel (102 -> 37 us at 672 x 64 x 12288).  Large M: the staged 128 x 64 tile
+  // kernel streams A in full 128-byte lines and wins -- 56 vs 96 us at 11780 x 64 x 6144; the tall-skinny kernel's fragment-shaped loads
+  // are 64-byte row segments, and it has no act 3 / 4 epilogue
+  if ((kernel == 0 || kernel == 3) && N <= 64 && g_gemm_ts && M <= 4096 && act != 3 && act != 4 && K >= 256) return {GEMM_TS, 0};
+  if (kernel == 0) {
+    // auto (measured on MI355X, profiles/r01_perf_ops_first.json, tools/gemm_bench.py): the pipelined 256x256 tile
+    // runs 1.25-1.4x the 128x128 one per CU; pick whichever loses less to wave quantisation over the 256 CUs
+    // (256x256: 1 WG/CU -> 256 slots per round; 128x128: 2 WG/CU -> 512 slots).  E.g. the lm_head^T product of the
+    // CE backward (4096 x 4096 x 128256) is exactly 256 big tiles = one full round.  Skinny N takes 128x64.
+    const int64_t tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
+    const int64_t tiles128 = ((M + 127) / 128) * ((N + 127) / 128);
+    // time in units of "one CU doing one 128x128 tile": a 256x256 round = 4 tiles of work at ~1.3-1.4x speed
+    const double t256 = (double)((tiles256 + 255) / 256) * (4.0 / 1.4);
+    const double t128 = (double)((tiles128 + 511) / 512) * 2.0;
+    const int big = g_gemm_big;
+    // the persistent form (next tile's first two k-tiles DMA'd under the current tile's tail, no pipeline drain between
+    // tiles) pays on short-K products, where prologue + epilogue are a visible share of a tile: +3-4 % at K = 1280
+    // (Whisper), +-1 % at K >= 4096 (profiles/r02_gemm_experiments.md)
+    if (N <= 64) kernel = 3;
+    // 4-wave kernel: faster k-loop, longer epilogue (64 fragments per wave) -- it wins from K = 4096 up unless the output is narrow
+    // (N = 1280 with a residual epilogue, Whisper fc2: 1084 vs 1124 TF for the 8-wave pipelined kernel, tools/gemm_enc_bench.py)
+    else if (t256 < t128) kernel = (K <= 2048) ? (int)g_gemm_big_shortk : ((big == 12 && N < 2048) ? 6 : big);
+    else kernel = g_gemm_small;
+    // mid-M (round 4): fewer 256 x 256 tiles than half the CUs and a K worth slicing -> the 4-wave kernel on K slices + the reduce
+    // launch.  Cost model in the same unit (one CU x one 128 x 128 x K tile, ~22 us at K = 4096): 1 / S of a big tile's 2.86, plus the
+    // slab stores, the launch boundary and the reduce pass (~20 us whatever K is) -- measured on the C4 shapes, tools/gemm_splitk_sweep.py
+    if (g_gemm_sk2 && act != 4 && tiles256 <= 128 && N >= 256 && K >= 2048 && g_gemm_ws.load() != nullptr &&
+        fits_descriptor(M, lda, 1, K) && fits_descriptor(N, ldb, 1, K)) {
+      const int nt = (int)(K / BK);
+      int S = (int)(256 / tiles256);
+      if (S > nt / 8) S = nt / 8;
+      if (S > 8) S = 8;
+      const double tsk = (4.0 / 1.4) / S + 4500.0 / (double)K;
+      if (S >= 2 && SK_CNT_BYTES + tiles256 * S * (int64_t)(256 * 256 * 4) <= g_gemm_ws_bytes && tsk < 0.95 * (t256 < t128 ? t256 : t128))
+        return {12, S};
+    }
+  }
+  // what a kernel cannot serve: the pipelined loops need two k-tiles, the descriptor forms operands that 32 bits address
+  if (kernel == 11 && K < 2 * BK) kernel = 1;
+  if (kernel == 7 && (K < 2 * BK || !fits_descriptor(M, lda, 256, K) || !fits_descriptor(N, ldb, 256, K))) kernel = 6;
+  if (kernel == 12 && (K < 2 * BK || (act != 4 && !(fits_descriptor(M, lda, 1, K) && fits_descriptor(N, ldb, 1, K))))) kernel = 6;
+  return {kernel, 0};
+}
+
+// the label of gemm_plan's answer (NUL-terminated, into out[out_bytes]): the name the per-kernel timers and profiles file the launch under
+extern "C" int slam_gemm_kernel_name(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int act, char* out, int64_t out_bytes) {
+  SLAM_CHECK_ARG(out != nullptr && out_bytes > 0, "slam_gemm_kernel_name: no output buffer");
+  SLAM_CHECK_ARG(M > 0 && N > 0 && K > 0 && act >= 0 && act <= 4, "slam_gemm_kernel_name: bad shape M=%ld N=%ld K=%ld or act %d", (long)M, (long)N, (long)K, act);
+  const GemmPlan pl = gemm_plan(M, N, K, lda, ldb, act);
+  const char* label = gemm_kernel_label(pl.kernel);
+  SLAM_CHECK_ARG(label != nullptr, "slam_gemm_kernel_name: bad config %d", pl.kernel);
+  const int n = pl.two_launch_slices ? snprintf(out, (size_t)out_bytes, "%s split-K x%d + reduce", label, pl.two_launch_slices)
+                                     : snprintf(out, (size_t)out_bytes, "%s", label);
+  SLAM_CHECK_ARG(n >= 0 && n < out_bytes, "slam_gemm_kernel_name: the label needs %d bytes, the buffer has %ld", n + 1, (long)out_bytes);
+  return 0;
+}
+
 extern "C" int slam_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                                  int64_t ldc, int64_t M, int64_t N, int64_t K, const float* bias,
                                  const void* residual, int64_t ldr, int64_t res_row_mod, int act,
@@ -1236,74 +1314,29 @@ extern "C" int slam_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int6
   p.bias = bias; p.res = (const bf16_t*)residual; p.ldr = ldr; p.res_mod = (int)res_row_mod;
   p.act = act; p.alpha = alpha; p.out_f32 = (out_dtype == SLAM_F32); p.accumulate = accumulate;
   p.C2 = nullptr; p.ldc2 = 0;
-  int want_two = 0;
   p.group_m = gemm_group_m_for(M, N, K);
   hipStream_t s = (hipStream_t)stream;
-  int cfg = g_gemm_cfg;
-  if ((cfg == 0 || cfg == 3) && N <= 64) {
-    int rc = 0;
-    if (launch_gemm_ts(p, s, &rc)) return rc;
-  }
-  const int big = g_gemm_big, big_shortk = g_gemm_big_shortk;
-  if (cfg == 0) {
-    // auto (measured on MI355X, profiles/r01_perf_ops_first.json, tools/gemm_bench.py): the pipelined 256x256 tile
-    // runs 1.25-1.4x the 128x128 one per CU; pick whichever loses less to wave quantisation over the 256 CUs
-    // (256x256: 1 WG/CU -> 256 slots per round; 128x128: 2 WG/CU -> 512 slots).  E.g. the lm_head^T product of the
-    // CE backward (4096 x 4096 x 128256) is exactly 256 big tiles = one full round.  Skinny N takes 128x64.
-    const int64_t tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
-    const int64_t tiles128 = ((M + 127) / 128) * ((N + 127) / 128);
-    // time in units of "one CU doing one 128x128 tile": a 256x256 round = 4 tiles of work at ~1.3-1.4x speed (ties go to the big tile)
-    const double t256 = (double)((tiles256 + 255) / 256) * (4.0 / 1.4);
-    const double t128 = (double)((tiles128 + 511) / 512) * 2.0;
-    // the persistent form (next tile's first two k-tiles DMA'd under the current tile's tail, no pipeline drain between
-    // tiles) pays on short-K products, where prologue + epilogue are a visible share of a tile: +3-4 % at K = 1280
-    // (Whisper), +-1 % at K >= 4096 (profiles/r02_gemm_experiments.md)
-    if (N <= 64) cfg = 3;
-    // 4-wave kernel: faster k-loop, longer epilogue (64 fragments per wave) -- it wins from K = 4096 up unless the output is narrow
-    // (N = 1280 with a residual epilogue, Whisper fc2: 1084 vs 1124 TF for the 8-wave pipelined kernel, tools/gemm_enc_bench.py)
-    else if (t256 < t128) cfg = (K <= 2048) ? big_shortk : ((big == 12 && N < 2048) ? 6 : big);
-    else cfg = g_gemm_small;
-    // mid-M (round 4): fewer 256 x 256 tiles than half the CUs and a K worth slicing -> the 4-wave kernel on K slices + the reduce
-    // launch.  Cost model in the same unit (one CU x one 128 x 128 x K tile, ~22 us at K = 4096): 1 / S of a big tile's 2.86, plus the
-    // slab stores, the launch boundary and the reduce pass (~20 us whatever K is) -- measured on the C4 shapes, tools/gemm_splitk_sweep.py
-    if (g_gemm_sk2 && tiles256 <= 128 && N >= 256 && K >= 2048 && g_gemm_ws.load() != nullptr &&
-        fits_descriptor(M, lda, 1, K) && fits_descriptor(N, ldb, 1, K)) {
-      const int nt = (int)(K / BK);
-      int S = (int)(256 / tiles256);
-      if (S > nt / 8) S = nt / 8;
-      if (S > 8) S = 8;
-      const double tsk = (4.0 / 1.4) / S + 4500.0 / (double)K;
-      if (S >= 2 && SK_CNT_BYTES + tiles256 * S * (int64_t)(256 * 256 * 4) <= g_gemm_ws_bytes && tsk < 0.95 * (t256 < t128 ? t256 : t128)) {
-        cfg = 12;
-        want_two = S;
-      }
-    }
-  }
-  switch (cfg) {
+  const GemmPlan plan = gemm_plan(M, N, K, lda, ldb, act);
+  switch (plan.kernel) {
+    case GEMM_TS: return launch_gemm_ts(p, s);
     case 1: return launch_gemm<128, 128, 2, 2>(p, s);
-    case 11:                                               // 128x128 tiles on the register-double-buffered pipeline (two workgroups per CU)
-      if (p.K < 2 * BK) return launch_gemm<128, 128, 2, 2>(p, s);
-      return launch_gemm<128, 128, 2, 2, 1>(p, s);
+    case 11: return launch_gemm<128, 128, 2, 2, 1>(p, s);   // 128x128 tiles on the register-double-buffered pipeline (two workgroups per CU)
     case 2: return launch_gemm<256, 128, 4, 2>(p, s);
     case 3: return launch_gemm<128, 64, 2, 2>(p, s);
     case 4: return launch_gemm<256, 256, 2, 4>(p, s);
     case 6:                                                // pipelined, phase A pinned before the barrier (shipped)
       if (g_gemm_probe) return launch_gemm<256, 256, 2, 4, 1, true>(p, s);
       return launch_gemm<256, 256, 2, 4, 1>(p, s);
-    case 7:                                                // persistent pipelined, descriptor DMA (auto: short-K products)
-      if (p.K < 2 * BK || !fits_descriptor(p.M, p.lda, 256, p.K) || !fits_descriptor(p.N, p.ldb, 256, p.K)) return launch_gemm<256, 256, 2, 4, 1>(p, s);
-      return launch_gemm_persist2<256, 256, 2, 4>(p, s);
+    case 7: return launch_gemm_persist2<256, 256, 2, 4>(p, s);   // persistent pipelined, descriptor DMA (auto: short-K products)
     // (round 5's cfg 8 -- 128 x 256 tiles, two workgroups per CU, hand-ordered, bit-identical to cfg 7 -- measured 26 % slower
     //  (profiles/r05_gemm_two_wg.md) and was removed in round 6 with its translation unit; git history keeps it)
     // (cfg 5 = compiler-placed barrier, 8-11 = timing ablations of the pipelined loop, 13 = register-staged 4-wave form,
     //  14-16 = ablations of the 4-wave loop: measured, recorded in profiles/r02_gemm_experiments.md, removed to keep the build short)
     case 12:                                               // 4 waves, hand-ordered k-loop
-      if (p.K < 2 * BK || !fits_descriptor(p.M, p.lda, 1, p.K) || !fits_descriptor(p.N, p.ldb, 1, p.K))
-        return launch_gemm<256, 256, 2, 4, 1>(p, s);
       if (g_gemm_probe) return launch_gemm_w4<256, 256, false, 0, true>(p, s);
-      return launch_gemm_w4<256, 256, false>(p, s, want_two);
+      return launch_gemm_w4<256, 256, false>(p, s, plan.two_launch_slices);
   }
-  slam_set_error("slam_gemm_bf16_nt: bad config %d", cfg);
+  slam_set_error("slam_gemm_bf16_nt: bad config %d", plan.kernel);
   return -1;
 }
 
@@ -1312,18 +1345,9 @@ extern "C" int slam_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int6
 // the host whether the AUTO rule would pick that kernel for the shape anyway and the operands fit its 32-bit descriptors; when it
 // does not, the host runs the plain product + slam_swiglu_fwd.
 extern "C" int slam_gemm_swiglu_supported(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
-  if (M <= 0 || N <= 0 || K < 2 * BK || K % 64 || N % 128 || K <= 2048 || N < 2048) return 0;
-  if (g_gemm_cfg != 0 && g_gemm_cfg != 12) return 0;
-  if (g_gemm_cfg == 0) {
-    if (g_gemm_big != 12) return 0;
-    const int64_t tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
-    const int64_t tiles128 = ((M + 127) / 128) * ((N + 127) / 128);
-    const double t256 = (double)((tiles256 + 255) / 256) * (4.0 / 1.4);
-    const double t128 = (double)((tiles128 + 511) / 512) * 2.0;
-    if (!(t256 < t128)) return 0;
-  }
+  if (M <= 0 || N <= 0 || K % 64 || N % 128 || K <= 2048 || N < 2048) return 0;
   if ((uint64_t)M * (uint64_t)lda * 2ull >= (1ull << 32) || (uint64_t)N * (uint64_t)ldb * 2ull >= (1ull << 32)) return 0;
-  return 1;
+  return gemm_plan(M, N, K, lda, ldb, 4).kernel == 12;
 }
 
 extern "C" int slam_gemm_swiglu_bf16_nt(const void* A, int64_t lda, const void* B_interleaved, int64_t ldb, void* GU, int64_t ldgu,

@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("SLAM_HIP_LIB") or os.path.join(_HERE, "libslamhip.so"
 ABI_VERSION = 2      # what SIGNATURES below was written for; _load() refuses any other library (include/slam_hip.h, csrc/capi_core.hip)
 BF16, F32 = 0, 1
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SWIGLU_BWD = 0, 1, 2, 3
+ACT_SWIGLU_FWD = 4   # slam_gemm_kernel_name only: the epilogue of slam_gemm_swiglu_bf16_nt (slam_gemm_bf16_nt takes 0..3)
 
 P, I64, I32, F, U64 = c_void_p, c_int64, c_int, c_float, ctypes.c_uint64
 
@@ -37,6 +38,8 @@ SIGNATURES = {
     "slam_logmel_fwd": [P, I64, P, I64, P, P, P, I64, P, P, I64, I32, P],
     "slam_gemm_bf16_nt": [P, I64, P, I64, P, I64, I64, I64, I64, P, P, I64, I64, I32, F, I32, I32, P],
     "slam_gemm_set_config": [I32],
+    "slam_gemm_get_config": [],
+    "slam_gemm_kernel_name": [I64, I64, I64, I64, I64, I32, c_char_p, I64],
     "slam_gemm_set_group_m": [I32],
     "slam_gemm_set_group_m_rule": [I32, I32, I32, I32],
     "slam_gemm_set_workspace": [P, I64],

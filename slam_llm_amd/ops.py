@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import lib
-from .lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SWIGLU_BWD, BF16, F32, call  # noqa: F401
+from .lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SWIGLU_BWD, ACT_SWIGLU_FWD, BF16, F32, call  # noqa: F401
 
 
 class KernelTimer:
@@ -77,24 +77,14 @@ def _ld(t: torch.Tensor) -> int:
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
-_GEMM_WS = {}   # device index -> workspace tensor of the split-K tail (kept alive for the life of the process)
+_GEMM_WS = {}   # device index -> workspace tensor of the K-sliced plans (kept alive for the life of the process)
 GEMM_WS_BYTES = 4096 + 512 * 256 * 256 * 4   # counters + 512 slabs of 256 KiB (the auto plans use <= 256; forced sweeps up to 512): 128 MiB of 288 GB
 
 
-# Round 4: the scratch buffer is registered at the first product of the process: the K-sliced forms for mid-M products (two-launch split-K
-# of the 4-wave kernel) and for N <= 64 products (tall-skinny kernel) are part of the auto rule.  SLAM_GEMM_SK2=0 / SLAM_GEMM_TS=0 switch
-# them off (A/B); the in-launch split-K TAIL of round 3 stays off by default (gemm_set_config(300 | 302..316)).
-_SPLITK_WANTED = True
-SK2_AUTO = os.environ.get("SLAM_GEMM_SK2", "1") != "0"
-TS_AUTO = os.environ.get("SLAM_GEMM_TS", "1") != "0"
-
-
 def _ensure_gemm_workspace(device: torch.device):
-    """the split-K tail of the 4-wave GEMM needs a caller-owned scratch buffer (slam_gemm_set_workspace); registered once per
-    process, on the first product after a plan was switched on (one process drives one GPU: a second device would need its own
-    library state)."""
-    if not _SPLITK_WANTED:
-        return
+    """the K-sliced forms of the auto rule (two-launch split-K of the 4-wave kernel for mid-M products, the tall-skinny kernel for
+    N <= 64) and the split-K tail need a caller-owned scratch buffer (slam_gemm_set_workspace); registered once per process, at its
+    first product (one process drives one GPU: a second device would need its own library state)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx in _GEMM_WS:
         return
@@ -105,6 +95,21 @@ def _ensure_gemm_workspace(device: torch.device):
     ws = torch.zeros(GEMM_WS_BYTES, dtype=torch.uint8, device=device)
     call("slam_gemm_set_workspace", _p(ws), GEMM_WS_BYTES)
     _GEMM_WS[idx] = ws
+
+
+def gemm_kernel_name(M: int, N: int, K: int, lda: Optional[int] = None, ldb: Optional[int] = None, act: int = ACT_NONE) -> str:
+    """the kernel the library runs this product on under the current knobs and workspace (dense operands unless lda / ldb are given):
+    slam_gemm_kernel_name, answered by the function that dispatches the launch"""
+    buf = ctypes.create_string_buffer(64)
+    call("slam_gemm_kernel_name", M, N, K, K if lda is None else lda, K if ldb is None else ldb, act, buf, len(buf))
+    return buf.value.decode()
+
+
+def _timed_gemm(M, N, K, lda, ldb, act, work, fn, nbytes):
+    """_timed under the product's kernel name (asked for only when a timer listens)"""
+    if TIMER is None:
+        return fn()
+    return TIMER.run(gemm_kernel_name(M, N, K, lda, ldb, act) + (f" [{M}x{N}x{K}]" if TIMER_SHAPES else ""), work, fn, nbytes)
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, *, bias=None,
@@ -121,13 +126,13 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
     od = F32 if out.dtype == torch.float32 else BF16
     _ensure_gemm_workspace(a.device)
     if (M <= SKINNY_MAX_M and bias is None and act == ACT_NONE and alpha == 1.0 and not accumulate and res_row_mod == 0
-            and _GEMM_CFG == 0):
+            and lib.raw().slam_gemm_get_config() == 0):
         return gemm_skinny(a, b, out, residual=residual)  # a few rows (decode): HBM-bound weight-streaming kernel
-    _timed(gemm_kernel_name(M, N, K) + (f" [{M}x{N}x{K}]" if TIMER_SHAPES else ""), 2.0 * M * N * (k_alg or K),
-           lambda: call("slam_gemm_bf16_nt", _p(a), _ld(a), _p(b), _ld(b), _p(out), _ld(out), M, N, K, _p(bias),
-                        _p(residual), _ld(residual) if residual is not None else 0, res_row_mod, act, alpha, od,
-                        1 if accumulate else 0, _s()),
-           nbytes=2.0 * (M * K + N * K) + M * N * (4 if od == F32 else 2))
+    _timed_gemm(M, N, K, _ld(a), _ld(b), act, 2.0 * M * N * (k_alg or K),
+                lambda: call("slam_gemm_bf16_nt", _p(a), _ld(a), _p(b), _ld(b), _p(out), _ld(out), M, N, K, _p(bias),
+                             _p(residual), _ld(residual) if residual is not None else 0, res_row_mod, act, alpha, od,
+                             1 if accumulate else 0, _s()),
+                nbytes=2.0 * (M * K + N * K) + M * N * (4 if od == F32 else 2))
     return out
 
 
@@ -150,113 +155,41 @@ def gemm_skinny(a, b, out, residual=None, b2=None, swiglu=False):
     return out
 
 
-_GEMM_CFG = 0
-_GEMM_NAMES = {1: "gemm_nt_kernel<128,128,2,2>", 11: "gemm_nt_pipe_kernel<128,128,2,2,1>", 2: "gemm_nt_kernel<256,128,4,2>", 3: "gemm_nt_kernel<128,64,2,2>",
-               4: "gemm_nt_kernel<256,256,2,4>", 6: "gemm_nt_pipe_kernel<256,256,2,4,1>", 7: "gemm_nt_persist2_kernel<256,256,2,4>",
-               12: "gemm_nt_w4_kernel<256,256,false,0>"}
-
-
-_GEMM_BIG = {"big": 12, "shortk": 7, "small": 1}
-if os.environ.get("SLAM_GEMM_SMALL"):        # sweeps: SLAM_GEMM_SMALL=1|11 (the 128x128 kernel of the auto rule)
-    call("slam_gemm_set_config", 600 + int(os.environ["SLAM_GEMM_SMALL"]))
-    _GEMM_BIG["small"] = int(os.environ["SLAM_GEMM_SMALL"])
-if os.environ.get("SLAM_GEMM_BIG"):          # sweeps: SLAM_GEMM_BIG=12 SLAM_GEMM_BIG_SHORTK=7 python bench.py ...
-    call("slam_gemm_set_config", 100 + int(os.environ["SLAM_GEMM_BIG"]))
-    _GEMM_BIG["big"] = int(os.environ["SLAM_GEMM_BIG"])
-if os.environ.get("SLAM_GEMM_BIG_SHORTK"):
-    call("slam_gemm_set_config", 200 + int(os.environ["SLAM_GEMM_BIG_SHORTK"]))
-    _GEMM_BIG["shortk"] = int(os.environ["SLAM_GEMM_BIG_SHORTK"])
-
-
-if not SK2_AUTO:
-    call("slam_gemm_set_config", 360)
-if not TS_AUTO:
-    call("slam_gemm_set_config", 370)
-if os.environ.get("SLAM_GEMM_SPLITK"):       # sweeps: off | auto | <slices>
-    _sk = os.environ["SLAM_GEMM_SPLITK"]
-    call("slam_gemm_set_config", 301 if _sk == "off" else (300 if _sk == "auto" else 300 + int(_sk)))
-
-
-
-def gemm_kernel_name(M: int, N: int, K: int = 1 << 30) -> str:
-    """which template instance slam_gemm_bf16_nt's auto rule launches for this shape (mirrors gemm_bf16.hip)"""
-    cfg = _GEMM_CFG
-    if cfg in (0, 3) and N <= 64 and M <= 4096 and TS_AUTO and 256 <= K < (1 << 30):
-        return "gemm_ts_kernel"
-    if cfg == 0:
-        tiles256 = ((M + 255) // 256) * ((N + 255) // 256)
-        tiles128 = ((M + 127) // 128) * ((N + 127) // 128)
-        t256 = ((tiles256 + 255) // 256) * (4.0 / 1.4)
-        t128 = ((tiles128 + 511) // 512) * 2.0
-        big = 6 if (_GEMM_BIG["big"] == 12 and N < 2048) else _GEMM_BIG["big"]
-        cfg = 3 if N <= 64 else ((_GEMM_BIG["shortk"] if K <= 2048 else big) if t256 < t128 else _GEMM_BIG["small"])
-        if N > 64 and SK2_AUTO and tiles256 <= 128 and N >= 256 and 2048 <= K < (1 << 30) and _GEMM_WS:      # mid-M: K-sliced 4-wave kernel + reduce launch
-            S = min(256 // tiles256, (K // 64) // 8, 8)
-            if S >= 2 and (4.0 / 1.4) / S + 4500.0 / K < 0.95 * min(t256, t128):
-                return f"gemm_nt_w4_kernel<256,256,false,0> split-K x{S} + reduce"
-    return _GEMM_NAMES[cfg]
-
-
 def gemm_set_config(cfg: int):
-    """0 = auto rule, 1 2 3 4 6 7 12 = force one kernel (tools / tests); 100 + v / 200 + v = which 256x256 kernel the auto rule uses
-    for K > 2048 / K <= 2048 (sweeps)"""
-    global _GEMM_CFG
-    global _SPLITK_WANTED
-    global SK2_AUTO, TS_AUTO
-    if 360 <= cfg <= 362:
-        SK2_AUTO = cfg != 360
-    if cfg in (370, 371):
-        TS_AUTO = cfg == 371
-    if cfg in (601, 611):
-        _GEMM_BIG["small"] = cfg - 600
-    elif cfg >= 300:    # 300 / 301 / 302..316: split-K tail auto / off / forced slices; 400 / 401: cycle stamps off / on
-        pass
-    elif cfg >= 100:
-        _GEMM_BIG["big" if cfg < 200 else "shortk"] = cfg % 100
-    else:
-        _GEMM_CFG = cfg
+    """0 = auto rule, 1 2 3 4 6 7 11 12 = force one kernel (tools / tests); the other codes of slam_gemm_set_config (include/slam_hip.h,
+    csrc/gemm_bf16.hip) tune the auto rule and its split-K plans (sweeps)"""
     call("slam_gemm_set_config", cfg)
 
 
-ATTN_HEAVY_FIRST = os.environ.get("SLAM_ATTN_HEAVY", "1") != "0"     # A/B: SLAM_ATTN_HEAVY=0 python bench.py (id order of causal attention workgroups)
-ATTN_QS = os.environ.get("SLAM_ATTN_QS", "1") != "0"                 # A/B: SLAM_ATTN_QS=0 (general softmax also for the LSE-less mask-free launches with a pre-scaled Q)
-if not ATTN_QS:
-    call("slam_attn_set_fwd_qf", 60)
-if not ATTN_HEAVY_FIRST:
-    call("slam_attn_set_fwd_qf", 50)
-if os.environ.get("SLAM_GEMM_GROUP_M"):
-    call("slam_gemm_set_group_m", int(os.environ["SLAM_GEMM_GROUP_M"]))
-if os.environ.get("SLAM_GEMM_GROUP_M_RULE"):      # sweeps: "12,4,4,8" = the rule's four values (short-K many columns, long-K narrow, wide K <= 4096, other)
-    call("slam_gemm_set_group_m_rule", *[int(x) for x in os.environ["SLAM_GEMM_GROUP_M_RULE"].split(",")])
-_ENV_DEFAULTS = dict(_GEMM_BIG, sk2=SK2_AUTO, ts=TS_AUTO, splitk=os.environ.get("SLAM_GEMM_SPLITK", "off"))
+# Sweeps and A/B runs override the library's tuning defaults through the environment, e.g. SLAM_GEMM_BIG=6 SLAM_GEMM_BIG_SHORTK=7 python
+# bench.py ...: variable -> (entry point, arguments), None = leave the default.  The defaults themselves live in csrc only.
+_CFG, _QF = "slam_gemm_set_config", "slam_attn_set_fwd_qf"
+_ENV_KNOBS = {
+    "SLAM_GEMM_SMALL": lambda v: (_CFG, (600 + int(v),)),        # 1 | 11: the 128x128 kernel of the auto rule
+    "SLAM_GEMM_BIG": lambda v: (_CFG, (100 + int(v),)),          # 6 | 7 | 12: its 256x256 kernel for K > 2048 ...
+    "SLAM_GEMM_BIG_SHORTK": lambda v: (_CFG, (200 + int(v),)),   # ... and for K <= 2048
+    "SLAM_GEMM_SK2": lambda v: (_CFG, (360,)) if v == "0" else None,   # 0: no two-launch split-K for mid-M products
+    "SLAM_GEMM_TS": lambda v: (_CFG, (370,)) if v == "0" else None,    # 0: N <= 64 products stay on the 128 x 64 tile kernel
+    "SLAM_GEMM_SPLITK": lambda v: (_CFG, (301 if v == "off" else (300 if v == "auto" else 300 + int(v)),)),   # split-K tail: off | auto | <slices>
+    "SLAM_GEMM_GROUP_M": lambda v: ("slam_gemm_set_group_m", (int(v),)),   # 8 restores the one-size raster of rounds 1-5 (0 / unset = per-shape rule)
+    "SLAM_GEMM_GROUP_M_RULE": lambda v: ("slam_gemm_set_group_m_rule", tuple(int(x) for x in v.split(","))),   # "12,4,4,8" = short-K many columns, long-K narrow, wide K <= 4096, other
+    "SLAM_ATTN_HEAVY": lambda v: (_QF, (50,)) if v == "0" else None,   # 0: id order of causal attention workgroups
+    "SLAM_ATTN_QS": lambda v: (_QF, (60,)) if v == "0" else None,      # 0: general softmax also for the LSE-less mask-free launches with a pre-scaled Q
+}
+_ENV_TUNING = [t for t in (knob(os.environ[var]) for var, knob in _ENV_KNOBS.items() if os.environ.get(var)) if t is not None]
+for _entry, _args in _ENV_TUNING:
+    call(_entry, *_args)
 
 
 def reset_tuning():
     """every process-global tuning knob of the library (GEMM kernel choice, split-K plans, raster group, attention variants) back to
-    what this process started with (the shipped defaults, or the SLAM_GEMM_* environment of a sweep).  tests/conftest.py calls it
-    before every GPU test so that a test which dies between `gemm_set_config(x)` and its own restore cannot change what the tests
-    behind it measure (VERDICT r4 weak #1c)."""
-    d = _ENV_DEFAULTS
-    call("slam_reset_tuning")    # the library's own defaults (one place: csrc), then this process's environment overrides on top
+    what this process started with (the shipped defaults, or the SLAM_GEMM_* / SLAM_ATTN_* environment of a sweep).  tests/conftest.py
+    calls it before every GPU test so that a test which dies between `gemm_set_config(x)` and its own restore cannot change what the
+    tests behind it measure."""
+    call("slam_reset_tuning")    # the library's own defaults (one place: csrc)
     call("slam_set_dropout_salt", None)
-    gemm_set_config(0)
-    gemm_set_config(100 + d["big"])
-    gemm_set_config(200 + d["shortk"])
-    gemm_set_config(600 + d["small"])
-    gemm_set_config(361 if d["sk2"] else 360)
-    gemm_set_config(371 if d["ts"] else 370)
-    gemm_set_config(301 if d["splitk"] == "off" else (300 if d["splitk"] == "auto" else 300 + int(d["splitk"])))
-    gemm_set_config(320 + 4)     # split-K tail auto plan: last round <= 32 tiles ...
-    gemm_set_config(340 + 2)     # ... into at most 2 slices
-    gemm_set_config(400)         # cycle stamps off
-    if os.environ.get("SLAM_GEMM_GROUP_M"):       # A/B: SLAM_GEMM_GROUP_M=8 restores the one-size raster of rounds 1-5 (0 / unset = per-shape rule)
-        call("slam_gemm_set_group_m", int(os.environ["SLAM_GEMM_GROUP_M"]))
-    if os.environ.get("SLAM_GEMM_GROUP_M_RULE"):
-        call("slam_gemm_set_group_m_rule", *[int(x) for x in os.environ["SLAM_GEMM_GROUP_M_RULE"].split(",")])
-    call("slam_attn_set_bwd_variant", 0)
-    # auto fragments, DMA tiles, XCD-aware numbering, mask-free instantiation, transposing reads, heaviest block first, pre-scaled Q in LSE-less launches
-    for knob in (0, 11, 21, 31, 41, 51 if ATTN_HEAVY_FIRST else 50, 61 if ATTN_QS else 60):
-        call("slam_attn_set_fwd_qf", knob)
+    for entry, args in _ENV_TUNING:
+        call(entry, *args)
 
 
 # ------------------------------------------------------------------------------------------------ mel
@@ -768,8 +701,8 @@ def interleave_gate_up(w: torch.Tensor) -> torch.Tensor:
 
 
 def gemm_swiglu_supported(M: int, N: int, K: int, lda: int, ldb: int) -> bool:
-    """does slam_gemm_swiglu_bf16_nt serve this shape (the auto rule runs the 4-wave kernel on it)?"""
-    return _GEMM_CFG in (0, 12) and lib.raw().slam_gemm_swiglu_supported(M, N, K, lda, ldb) == 1
+    """does slam_gemm_swiglu_bf16_nt serve this shape (the rule runs the 4-wave kernel on it)?"""
+    return lib.raw().slam_gemm_swiglu_supported(M, N, K, lda, ldb) == 1
 
 
 def gemm_swiglu(a: torch.Tensor, b_il: torch.Tensor, gu: torch.Tensor, h: torch.Tensor):
@@ -777,9 +710,9 @@ def gemm_swiglu(a: torch.Tensor, b_il: torch.Tensor, gu: torch.Tensor, h: torch.
     M, K = a.shape
     N = b_il.shape[0]
     _ensure_gemm_workspace(a.device)
-    _timed(_GEMM_NAMES[12] + (f" [{M}x{N}x{K}]" if TIMER_SHAPES else ""), 2.0 * M * N * K,
-           lambda: call("slam_gemm_swiglu_bf16_nt", _p(a), _ld(a), _p(b_il), _ld(b_il), _p(gu), _ld(gu), _p(h), _ld(h), M, N, K, _s()),
-           nbytes=2.0 * (M * K + N * K) + 2.0 * M * N + 1.0 * M * N)
+    _timed_gemm(M, N, K, _ld(a), _ld(b_il), ACT_SWIGLU_FWD, 2.0 * M * N * K,
+                lambda: call("slam_gemm_swiglu_bf16_nt", _p(a), _ld(a), _p(b_il), _ld(b_il), _p(gu), _ld(gu), _p(h), _ld(h), M, N, K, _s()),
+                nbytes=2.0 * (M * K + N * K) + 2.0 * M * N + 1.0 * M * N)
     return gu, h
 
 

@@ -2,6 +2,8 @@
 (no compute calls here)."""
 import os
 import re
+import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,3 +61,114 @@ def test_product_never_imports_the_oracle():
             if f.endswith(".py"):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", txt, flags=re.M), f"{f} imports the oracle"
+
+
+# ---- which kernel a GEMM runs on: slam_gemm_kernel_name (host code only: no device is touched) ---------------------------------------
+W4, PIPE, PERSIST = "gemm_nt_w4_kernel<256,256,false,0>", "gemm_nt_pipe_kernel<256,256,2,4,1>", "gemm_nt_persist2_kernel<256,256,2,4>"
+T128, T128x64, TS = "gemm_nt_kernel<128,128,2,2>", "gemm_nt_kernel<128,64,2,2>", "gemm_ts_kernel"
+# (forced config, M, N, K, label) for dense operands and no workspace, recorded from the Python copy of the selection rule that
+# ops.gemm_kernel_name was before the library answered the question itself: the step's own products, the t256 == t128 tie (257 x 204800),
+# N <= 64 on both sides of M = 4096 and of K = 256, N < 2048 against N >= 2048 at K > 2048, K = 2048 against 2112, products the 128 x 128
+# tile wins, and two shapes under every forced config.  No mid-M split-K candidate (tiles256 <= 128 and N >= 256 and K >= 2048): whether
+# those split depends on a registered workspace, and the GPU tests assert their labels (test_ops_gpu.py: test_gemm_mid_m_rule_*).
+FROZEN_LABELS = [
+    (0, 11780, 4096, 4096, W4), (0, 11780, 6144, 4160, W4), (0, 11780, 4096, 14336, W4), (0, 11780, 28672, 4096, W4),
+    (0, 6000, 3840, 1280, PERSIST), (0, 6000, 5120, 1280, PERSIST), (0, 12000, 3840, 1280, PERSIST), (0, 12000, 1280, 5120, PIPE),
+    (0, 12000, 5120, 1280, PERSIST), (0, 12000, 1280, 1280, PERSIST),
+    (0, 4096, 128256, 4096, W4), (0, 4096, 4096, 128256, W4), (0, 128256, 4096, 4096, W4),
+    (0, 257, 204800, 4096, T128), (0, 257, 204800, 1280, T128),
+    (0, 672, 64, 12288, TS), (0, 4096, 64, 6144, TS), (0, 4097, 64, 6144, T128x64), (0, 11780, 64, 6144, T128x64), (0, 672, 64, 192, T128x64),
+    (0, 672, 32, 256, TS), (0, 11780, 32, 4096, T128x64),
+    (0, 11780, 1280, 5120, PIPE), (0, 11780, 2044, 4096, PIPE), (0, 11780, 2048, 4096, W4),
+    (0, 11780, 4096, 2048, PERSIST), (0, 11780, 4096, 2112, W4),
+    (0, 256, 256, 128, T128), (0, 300, 260, 64, T128), (0, 6000, 1280, 1280, T128), (0, 1000, 768, 1024, T128), (0, 4352, 4096, 1024, PERSIST),
+    (0, 70, 4096, 1024, T128), (0, 129, 132, 640, T128),
+    (1, 512, 512, 128, T128), (1, 1000, 768, 4096, T128),
+    (2, 512, 512, 128, "gemm_nt_kernel<256,128,4,2>"), (2, 1000, 768, 4096, "gemm_nt_kernel<256,128,4,2>"),
+    (3, 512, 512, 128, T128x64), (3, 1000, 768, 4096, T128x64),
+    (4, 512, 512, 128, "gemm_nt_kernel<256,256,2,4>"), (4, 1000, 768, 4096, "gemm_nt_kernel<256,256,2,4>"),
+    (6, 512, 512, 128, PIPE), (6, 1000, 768, 4096, PIPE),
+    (7, 512, 512, 128, PERSIST), (7, 1000, 768, 4096, PERSIST),
+    (11, 512, 512, 128, "gemm_nt_pipe_kernel<128,128,2,2,1>"), (11, 1000, 768, 4096, "gemm_nt_pipe_kernel<128,128,2,2,1>"),
+    (12, 512, 512, 128, W4), (12, 1000, 768, 4096, W4),
+]
+
+
+def frozen_label_mismatches(ops):
+    bad = []
+    try:
+        for cfg, M, N, K, want in FROZEN_LABELS:
+            ops.gemm_set_config(cfg)
+            got = ops.gemm_kernel_name(M, N, K)
+            if got != want:
+                bad.append((cfg, M, N, K, got, want))
+    finally:
+        ops.gemm_set_config(0)
+    return bad
+
+
+def test_gemm_kernel_labels_did_not_move():
+    from slam_llm_amd import lib, ops
+    assert len(FROZEN_LABELS) >= 40
+    for cfg, M, N, K, _ in FROZEN_LABELS:
+        tiles256 = ((M + 255) // 256) * ((N + 255) // 256)
+        assert not (cfg == 0 and tiles256 <= 128 and N >= 256 and K >= 2048), (M, N, K)
+    try:
+        assert frozen_label_mismatches(ops) == []
+        assert lib.raw().slam_gemm_get_config() == 0
+    finally:
+        ops.reset_tuning()
+
+
+def test_gemm_kernel_labels_follow_the_fall_backs():
+    """what the dispatch does and the Python copy of the rule did not know: the pipelined loops need two k-tiles, the descriptor kernels
+    operands that 32 bits address, the tall-skinny kernel K >= 256 and an epilogue other than act 3"""
+    from slam_llm_amd import ops
+    try:
+        ops.gemm_set_config(7)
+        assert ops.gemm_kernel_name(512, 512, 64) == PIPE
+        ops.gemm_set_config(11)
+        assert ops.gemm_kernel_name(512, 512, 64) == T128
+        ops.gemm_set_config(12)
+        assert 70000 * 32768 * 2 > 2 ** 32
+        assert ops.gemm_kernel_name(70000, 512, 4096, lda=32768) == PIPE
+        assert ops.gemm_kernel_name(70000, 512, 4096) == W4
+        ops.gemm_set_config(0)
+        assert ops.gemm_kernel_name(672, 64, 12288) == TS
+        assert ops.gemm_kernel_name(672, 64, 12288, act=ops.ACT_SWIGLU_BWD) == T128x64
+        assert ops.gemm_kernel_name(672, 64, 192) == T128x64
+    finally:
+        ops.reset_tuning()
+
+
+def test_reset_tuning_restores_the_library_defaults():
+    from slam_llm_amd import lib, ops
+    try:
+        for code in (6, 106, 207, 611, 360, 370, 302, 336, 348, 401):
+            ops.gemm_set_config(code)
+        lib.call("slam_gemm_set_group_m", 5)
+        lib.call("slam_gemm_set_group_m_rule", 3, 5, 7, 2)
+        assert lib.raw().slam_gemm_get_config() == 6 and ops.gemm_kernel_name(11780, 4096, 4096) == PIPE
+        ops.gemm_set_config(0)      # (the auto rule under the changed knobs: the 8-wave kernel for long K, no tall-skinny kernel)
+        assert ops.gemm_kernel_name(11780, 4096, 4096) == PIPE and ops.gemm_kernel_name(672, 64, 12288) == T128x64
+        ops.gemm_set_config(6)
+        ops.reset_tuning()
+        assert lib.raw().slam_gemm_get_config() == 0
+        assert frozen_label_mismatches(ops) == []
+    finally:
+        ops.reset_tuning()
+
+
+def test_reset_tuning_replays_the_environment_overrides():
+    """a sweep's SLAM_GEMM_* environment holds at import and again after reset_tuning() (a fresh child process: the overrides are read once, at import)"""
+    child = (
+        "from slam_llm_amd import ops\n"
+        "def labels(): return [ops.gemm_kernel_name(11780, 4096, 4096), ops.gemm_kernel_name(672, 64, 12288)]\n"
+        "first = labels()\n"
+        "ops.gemm_set_config(112); ops.gemm_set_config(371); ops.gemm_set_config(7)\n"
+        "ops.reset_tuning()\n"
+        "print(repr((first, labels())))\n")
+    env = dict(os.environ, SLAM_GEMM_BIG="6", SLAM_GEMM_TS="0")
+    out = subprocess.run([sys.executable, "-c", child], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.strip().splitlines()[-1] == repr(([PIPE, T128x64], [PIPE, T128x64]))

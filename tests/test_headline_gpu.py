@@ -239,7 +239,7 @@ def _headline_case(dev, encoder, B, enc_layers, llm_layers, keep=None):
         keep.update(W=W, cfg=dict(cfg), ob=ob, grads=grads, loss_ref=loss_ref)
     del W
     model.train()
-    assert ops._GEMM_CFG == 0, "the headline test runs under the AUTO GEMM rule"
+    assert ops.lib.raw().slam_gemm_get_config() == 0, "the headline test runs under the AUTO GEMM rule"
     gb = {k: v.to(dev) for k, v in ob.items() if k != "audio_mel"}
     gb["audio"] = audio.to(dev)                                   # GPU log-mel front end, like bench.py
     ops.TIMER = ops.KernelTimer()
@@ -352,7 +352,7 @@ def test_gemm_at_bench_shapes(dev, M, N, K, bias, res):
     b = _rand_bf16((N, K), dev, 2, K ** -0.5)
     bias_t = torch.randn(N, device=dev) if bias else None
     res_t = _rand_bf16((M, N), dev, 3) if res else None
-    assert ops._GEMM_CFG == 0
+    assert ops.lib.raw().slam_gemm_get_config() == 0
     name = ops.gemm_kernel_name(M, N, K)
     assert ("persist2" in name) if K <= 2048 else ("w4" in name), name
     out = ops.gemm_nt(a, b, bias=bias_t, residual=res_t)

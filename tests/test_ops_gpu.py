@@ -217,19 +217,27 @@ def test_gemm_swiglu_backward_epilogue_equals_separate_pass(dev, M, F_, K):
     assert float((got != want).float().mean()) < 0.01
 
 
-@pytest.mark.parametrize("M,F_,K,forced", [(772, 1024, 4096, True), (600, 1088, 2112, True), (11780, 14336, 4096, False)])
+@pytest.mark.parametrize("M,F_,K,forced", [(772, 1024, 4096, True), (600, 1088, 2112, True), (11780, 14336, 4096, False), (3000, 1536, 2112, 106)])
 def test_gemm_swiglu_forward_epilogue_equals_separate_pass(dev, M, F_, K, forced):
     """act 4 (slam_gemm_swiglu_bf16_nt): ONE launch writes the [gate64 | up64]-block stash and h = silu(gate) * up.  Against
     gemm_nt (same 4-wave kernel, plain [gate | up] weight) -> swiglu_fwd: the product's elements are the same dot products in the
     same k order and silu runs on the bf16-rounded values in both, so BOTH outputs must be bit-identical once the column blocks are
     put back in order.  Shapes: thin M tail (772 = 3 x 256 + 4), a ragged last tile row (600) with a ragged last tile column
     (N = 2176 = 8.5 x 256), an odd number of k-tiles (K = 33 x 64); the Llama-3-8B shape of the C3 batch under the AUTO rule.  Then the backward
-    elementwise pass reading the block layout == reading the plain one."""
+    elementwise pass reading the block layout == reading the plain one.  forced = 106: a 12 x 12 tile grid (more tiles than the mid-M plan
+    slices) on which the AUTO rule picks the 4-wave kernel; with the rule's long-K kernel switched to the 8-wave pipelined one
+    (gemm_set_config(106)) neither the SwiGLU entry point nor the kernel label may claim the 4-wave kernel, and back under the default
+    both do."""
     ops = _ops()
     x = rnd((M, K), dev, seed=51)
     w = rnd((2 * F_, K), dev, seed=52, std=K ** -0.5)
     try:
-        if forced:
+        if forced == 106:
+            ops.gemm_set_config(106)
+            assert not ops.gemm_swiglu_supported(M, 2 * F_, K, K, K)
+            assert "w4" not in ops.gemm_kernel_name(M, 2 * F_, K)
+            ops.gemm_set_config(112)
+        elif forced:
             ops.gemm_set_config(12)
         assert ops.gemm_swiglu_supported(M, 2 * F_, K, K, K)
         gu_ref = ops.gemm_nt(x, w)
@@ -240,6 +248,7 @@ def test_gemm_swiglu_forward_epilogue_equals_separate_pass(dev, M, F_, K, forced
         h = torch.full((M, F_), float("nan"), dtype=torch.bfloat16, device=dev)
         ops.gemm_swiglu(x, wil, gu_il, h)
     finally:
+        ops.gemm_set_config(112)
         ops.gemm_set_config(0)
     blocks = gu_il.view(M, F_ // 64, 2, 64)
     gu_back = torch.cat([blocks[:, :, 0].reshape(M, F_), blocks[:, :, 1].reshape(M, F_)], dim=1)
@@ -247,6 +256,26 @@ def test_gemm_swiglu_forward_epilogue_equals_separate_pass(dev, M, F_, K, forced
     assert torch.equal(h, h_ref), f"h differs in {int((h != h_ref).sum())} elements"
     dh = rnd((M, F_), dev, seed=53)
     assert torch.equal(ops.swiglu_bwd(gu_il, dh, interleaved=True), ops.swiglu_bwd(gu_ref, dh))
+
+
+def test_gemm_timer_files_each_launch_under_the_kernel_that_ran(dev):
+    """ops.TIMER keys a GEMM launch by the library's own answer for that product -- shape, LEADING DIMENSIONS and act, as launched -- and
+    no label is built (nothing recorded) when no timer is set"""
+    ops = _ops()
+    a, b = rnd((256, 128), dev, seed=71), rnd((256, 128), dev, seed=72)
+    M, N, K = 300, 200, 256
+    a_view, b_view = rnd((M, 512), dev, seed=73)[:, 64:64 + K], rnd((N, 320), dev, seed=74)[:, :K]   # column slices: lda = 512, ldb = 320 > K
+    saved = ops.TIMER
+    try:
+        for operands, want in (((a, b), ops.gemm_kernel_name(256, 256, 128)), ((a_view, b_view), ops.gemm_kernel_name(M, N, K, 512, 320))):
+            ops.TIMER = timer = ops.KernelTimer()
+            ops.gemm_nt(*operands)
+            assert {name: len(runs) for name, runs in timer.rec.items()} == {want: 1}
+        ops.TIMER = None
+        ops.gemm_nt(a, b)
+        assert {name: len(runs) for name, runs in timer.rec.items()} == {want: 1}
+    finally:
+        ops.TIMER = saved
 
 
 def test_gemm_swiglu_forward_is_refused_where_the_4_wave_kernel_does_not_run(dev):
@@ -342,7 +371,7 @@ def test_gemm_mid_m_rule_slices_k_and_matches_unsliced(dev, M, N, K, epi):
         out = base.clone() if f32 else torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
         ops.gemm_nt(a, b, out=out, bias=bias, residual=res, act=act, accumulate=f32)
         return out
-    assert ops._GEMM_CFG == 0
+    assert ops.lib.raw().slam_gemm_get_config() == 0
     run()      # (registers the scratch buffer on the first product of the process)
     assert "split-K" in ops.gemm_kernel_name(M, N, K), ops.gemm_kernel_name(M, N, K)
     s1, s2 = run(), run()
