@@ -451,6 +451,20 @@ int slam_attn_decode_qknorm(const void* qkv, int64_t ld, const void* lora_b, int
                             int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
                             const float* q_norm_w, const float* k_norm_w, float eps, void* stream);
 
+/* slam_attn_decode_qknorm over a prompt SPAN per batch item (right-padded or both-sided padded prompt batches): the prompt keys
+ * of item b are the slots [prompt_start[b], prompt_end[b]) of its [Tp, Hkv*D] block, key i of the span at physical slot
+ * prompt_start[b] + i; the generated keys follow the span.  prompt_end: [B] int32, or null = Tp for every item (then bit-identical
+ * to slam_attn_decode_qknorm, and through it to slam_attn_decode_bias / slam_attn_decode).  Bias, q/k norm and LoRA exactly as
+ * slam_attn_decode_qknorm.  prompt_start / prompt_end are DEVICE arrays: their values cannot be checked at the call.  The kernel
+ * reads an end above Tp as Tp and an end below the start as an empty span (the new token then attends to the generated keys and
+ * itself only); a negative start is the caller's error, as in the three entry points above. */
+int slam_attn_decode_span(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                          const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt,
+                          const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen, int32_t* ancestors,
+                          const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R, int64_t beams,
+                          int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
+                          const float* q_norm_w, const float* k_norm_w, float eps, const int32_t* prompt_end, void* stream);
+
 /* Per-head RMSNorm + RoPE, in place on the Hq + Hkv adjacent heads at columns [col0, col0 + (Hq+Hkv)*D) of qkv [B*T, ld] bf16
  * (HF Qwen3Attention.forward: q_norm / k_norm then apply_rotary_pos_emb; Qwen3RMSNorm.forward for the two roundings).  Heads
  * < Hq take q_weight, the others k_weight ([D] fp32).  positions: [B*T] int32 row of the cos/sin tables ([P, D/2] fp32), or null

@@ -9,7 +9,8 @@
 //     that thousands of waves have loads in flight whatever N is; all reductions run in a fixed order.
 //   * decode_rope_append_kernel: RoPE on the new q/k (positions per row), append k/v to the generated-token cache.
 //   * attn_decode_kernel: one query per row against [prompt KV of the row's batch item | generated KV reached
-//     through the beam ancestor table].  Beam hypotheses SHARE the prompt KV (stored once per batch item) and the
+//     through the beam ancestor table].  The prompt keys of an item are the slots [start, end) of its prompt KV block
+//     (left and right padding stay outside the span).  Beam hypotheses SHARE the prompt KV (stored once per batch item) and the
 //     generated KV is never re-ordered: a [rows, G] int table says which physical row wrote slot j of each
 //     hypothesis' history (HF re-orders the whole cache with index_select every step).
 #include "common.h"
@@ -244,7 +245,8 @@ struct DecodeAttnParams {
   const float* qnorm; const float* knorm; float norm_eps;  // [D] fp32 per-head RMSNorm weights of q and k (Qwen3) or null
   const float* cosT; const float* sinT; const int* positions;  // RoPE tables [P, D/2], position per row
   const bf16_t* Kp; const bf16_t* Vp;  // prompt KV [B, Tp, Hkv*D]
-  const int* start;                // [B] first valid prompt slot (left padding)
+  const int* start;                // [B] first valid prompt slot (left padding), null = 0
+  const int* end;                  // [B] one past the last valid prompt slot (right padding), null = Tp
   bf16_t* Kg; bf16_t* Vg;          // generated KV [R, G, Hkv*D]
   int* anc;                        // [R, G] physical row that wrote slot j of hypothesis r
   const int* gen_count_dev; int gen_count_host;  // generated tokens cached BEFORE this step's append
@@ -385,7 +387,8 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
   const int c = lane % LPK, gid = wave * GPW + lane / LPK;
   const int n_prev = p.gen_count_dev ? *p.gen_count_dev : p.gen_count_host;  // slot of the new token
   const int start = p.start ? p.start[item] : 0;
-  const int np = p.Tp - start;
+  const int end = p.end ? min(p.end[item], p.Tp) : p.Tp;   // a span never reaches past the block it indexes
+  const int np = max(end - start, 0);   // prompt keys of this item: physical slots start .. end
   const int n_keys = np + n_prev;   // cached keys; the new token is handled from LDS by group 0
   const int64_t HD = (int64_t)p.Hkv * D;
   for (int j = tid; j < n_prev; j += NW * 64) anc_s[j] = p.anc[(int64_t)r * p.G + j];
@@ -617,7 +620,7 @@ extern "C" int slam_gemm_skinny_bf16_nt(const void* A, int64_t lda, const void* 
 
 static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
                             const float* qkv_bias, const float* q_norm_w, const float* k_norm_w, float norm_eps,
-                            const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen,
+                            const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, const int32_t* prompt_end, void* k_gen, void* v_gen,
                             int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R,
                             int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream) {
   SLAM_CHECK_ARG(qkv && cos_table && sin_table && positions && k_prompt && v_prompt && k_gen && v_gen && ancestors && O,
@@ -634,7 +637,7 @@ static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const v
   p.bias = qkv_bias;
   p.qnorm = q_norm_w; p.knorm = k_norm_w; p.norm_eps = norm_eps;
   p.cosT = cos_table; p.sinT = sin_table; p.positions = positions;
-  p.Kp = (const bf16_t*)k_prompt; p.Vp = (const bf16_t*)v_prompt; p.start = prompt_start;
+  p.Kp = (const bf16_t*)k_prompt; p.Vp = (const bf16_t*)v_prompt; p.start = prompt_start; p.end = prompt_end;
   p.Kg = (bf16_t*)k_gen; p.Vg = (bf16_t*)v_gen; p.anc = ancestors;
   p.gen_count_dev = gen_count_dev; p.gen_count_host = (int)gen_count; p.O = (bf16_t*)O; p.ldo = ldo;
   p.beams = (int)beams; p.Tp = (int)Tp; p.G = (int)G; p.Hq = (int)Hq; p.Hkv = (int)Hkv;
@@ -653,7 +656,7 @@ extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b,
                                 int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv,
                                 int64_t D, float scale, void* stream) {
   return attn_decode_impl("slam_attn_decode", qkv, ld, lora_b, ldlb, lora_r, nullptr, nullptr, nullptr, 0.f, cos_table, sin_table, positions,
-                          k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O, ldo, R,
+                          k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O, ldo, R,
                           beams, Tp, G, Hq, Hkv, D, scale, stream);
 }
 
@@ -664,7 +667,7 @@ extern "C" int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lo
                                      void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
                                      int64_t Hkv, int64_t D, float scale, const float* qkv_bias, void* stream) {
   return attn_decode_impl("slam_attn_decode_bias", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, nullptr, nullptr, 0.f, cos_table,
-                          sin_table, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
                           ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
 }
 
@@ -677,6 +680,19 @@ extern "C" int slam_attn_decode_qknorm(const void* qkv, int64_t ld, const void* 
                                        int64_t Hkv, int64_t D, float scale, const float* qkv_bias, const float* q_norm_w,
                                        const float* k_norm_w, float eps, void* stream) {
   return attn_decode_impl("slam_attn_decode_qknorm", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
-                          sin_table, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors, gen_count_dev, gen_count,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count,
                           O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
+}
+/* slam_attn_decode_qknorm over a prompt span per item: keys [prompt_start[item], prompt_end[item]) of the prompt block (right-padded
+ * batches); a null prompt_end means Tp. */
+extern "C" int slam_attn_decode_span(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                                     const float* cos_table, const float* sin_table, const int32_t* positions,
+                                     const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
+                                     void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count,
+                                     void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
+                                     int64_t Hkv, int64_t D, float scale, const float* qkv_bias, const float* q_norm_w,
+                                     const float* k_norm_w, float eps, const int32_t* prompt_end, void* stream) {
+  return attn_decode_impl("slam_attn_decode_span", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, prompt_end, k_gen, v_gen, ancestors, gen_count_dev,
+                          gen_count, O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
 }

@@ -19,6 +19,7 @@ views).  Data layout in HBM (sized for 288 GB):
 """
 from __future__ import annotations
 
+import logging
 import math
 from types import SimpleNamespace
 
@@ -32,6 +33,9 @@ from . import ops, trace
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, round_up
 
 import os as _os
+
+logger = logging.getLogger(__name__)
+_RIGHT_PAD_WARNED = [False]   # generate(): the right-padding warning is logged once per process
 # SwiGLU backward inside the down_proj dX GEMM epilogue (act = 3).  Correct and tested, but measured neutral-to-slower
 # on the C3 step (A/B in one process: 444.2-446.4 ms fused vs 443.7-444.6 ms separate pass): with one 256x256 workgroup
 # per CU the exp-heavy epilogue is not overlapped with MFMA work.  Off unless SLAM_FUSED_SWIGLU_BWD=1.
@@ -2447,18 +2451,26 @@ class HipLlamaLora(nn.Module):
         return ops.gemm_nt(hN, self.lm_head, out_dtype=torch.float32)
 
     @torch.no_grad()
-    def prefill(self, h: torch.Tensor, B: int, T: int, attention_mask: torch.Tensor, max_new_tokens: int, beams: int = 1):
-        """Run the prompt (h [B*T, d] bf16, LEFT padded) and build the KV cache for B*beams hypotheses.  Rotary
-        positions follow HF generate(): cumsum(attention_mask) - 1 per row, NOT arange (which the training forward
-        uses).  Returns (next-token logits [B, V] fp32, cache)."""
+    def prefill(self, h: torch.Tensor, B: int, T: int, attention_mask: torch.Tensor, max_new_tokens: int, beams: int = 1,
+                right_pad_fix: bool = False):
+        """Run the prompt (h [B*T, d] bf16; rows padded on the left, on the right or on both sides) and build the KV cache for
+        B*beams hypotheses.  Rotary positions, the slot that gives the first logits and the positions of the generated tokens follow
+        decode.prompt_spans: HF generate()'s as the reference runs it by default (cumsum(attention_mask) - 1 on real slots, NOT arange,
+        which the training forward uses; on a right-padded row the first logits come from the pad query at T - 1), each row
+        as if alone and unpadded with right_pad_fix.  Returns (next-token logits [B, V] fp32, cache)."""
+        from . import decode
         cfg, st, dev = self.cfg, self.store, h.device
         d, Hq, Hkv, D = cfg["llm_dim"], cfg["llm_heads"], cfg["llm_kv_heads"], cfg["llm_head_dim"]
         M, R, G, Ln, eps = B * T, B * beams, max_new_tokens, len(self.layers), cfg["rms_eps"]
         am = attention_mask.to(device=dev, dtype=torch.int32)
-        if not bool((am[:, 1:] >= am[:, :-1]).all()) or not bool(am[:, -1].all()):
-            raise ValueError("generate(): the prompt batch must be left padded (speech_dataset.py:216-273 inference collator)")
-        positions = (am.cumsum(-1) - 1).clamp_(min=0).to(torch.int32).contiguous()
-        n_real = am.sum(-1).to(torch.int32)
+        sp = decode.prompt_spans(am, fix=right_pad_fix)
+        if not right_pad_fix and not _RIGHT_PAD_WARNED[0] and bool((sp.end < T).any()):
+            _RIGHT_PAD_WARNED[0] = True
+            logger.warning("generate(): the prompt batch has rows padded on the right; they are decoded the way the reference decodes "
+                           "them (first token from the pad query at the last slot, new positions from 1).  Set "
+                           "++model_config.generate_right_pad_fix=true (or generate(..., generate_right_pad_fix=True)) to decode every "
+                           "row as if it were alone and unpadded.")
+        positions = sp.positions
         cos, sin = self.rope(T + G)
         Tp64 = round_up(T, 64)
         key_mask = torch.zeros((B, Tp64), dtype=torch.uint8, device=dev)
@@ -2469,8 +2481,8 @@ class HipLlamaLora(nn.Module):
             Kp=torch.empty((Ln, B, T, Hkv * D), **kv), Vp=torch.empty((Ln, B, T, Hkv * D), **kv),
             Kg=torch.zeros((Ln, R, G, Hkv * D), **kv), Vg=torch.zeros((Ln, R, G, Hkv * D), **kv),
             anc=torch.arange(R, dtype=torch.int32, device=dev)[:, None].repeat(1, G).contiguous(),
-            start=(T - n_real).to(torch.int32).contiguous(),
-            next_pos=n_real.repeat_interleave(beams).contiguous(),
+            start=sp.start, end=sp.end,
+            next_pos=sp.next_pos.repeat_interleave(beams).contiguous(),
             n_dev=torch.zeros(1, dtype=torch.int32, device=dev), tok=torch.zeros(R, dtype=torch.int64, device=dev),
             graph=None, logits=None)
         for li, L in enumerate(self.layers):
@@ -2487,7 +2499,7 @@ class HipLlamaLora(nn.Module):
             ops.attn_fwd(qkv[:, : Hq * D], qkv[:, Hq * D:(Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:], B, T, Hq, Hkv, D, True, D ** -0.5,
                          key_mask=key_mask, want_lse=False, out=o_ext[:, : Hq * D])
             h = self._mlp_block(L, L.o.forward(o_ext, st, residual=h))
-        last = h.view(B, T, -1)[:, T - 1].contiguous()
+        last = h.view(B, T, -1)[torch.arange(B, device=dev), sp.first_row].contiguous()
         return self._next_logits(last), cache
 
     @torch.no_grad()
@@ -2523,7 +2535,8 @@ class HipLlamaLora(nn.Module):
             o_ext = L.o.new_input(R)
             ops.attn_decode(qkv, lora_b, lora_r, cos, sin, cache.next_pos, cache.Kp[li], cache.Vp[li], cache.start,
                             cache.Kg[li], cache.Vg[li], cache.anc, cache.n_dev, cache.n, cache.beams, Hq, Hkv, D,
-                            D ** -0.5, o_ext, qkv_bias=L.bias, qk_norm=(L.q_norm, L.k_norm, eps) if self.qk_norm else None)
+                            D ** -0.5, o_ext, qkv_bias=L.bias, qk_norm=(L.q_norm, L.k_norm, eps) if self.qk_norm else None,
+                            prompt_end=cache.end)
             h_mid = L.o.forward(o_ext, st, residual=h)
             x2 = L.gu.new_input(R)
             ops.rmsnorm_fwd(h_mid, L.ln2, eps, out=x2[:, :d])
@@ -3222,7 +3235,8 @@ class SlamHipModel(nn.Module):
         fwd_kwargs["inference_mode"] = True
         embeds, attention_mask = self.forward(input_ids=input_ids, attention_mask=attention_mask, **fwd_kwargs)
         B, T, d = embeds.shape
-        logits0, cache = self.llm.prefill(embeds.reshape(B * T, d), B, T, attention_mask, max_new, beams=num_beams)
+        fix = bool(kwargs.get("generate_right_pad_fix", self.cfg.get("generate_right_pad_fix", False)))
+        logits0, cache = self.llm.prefill(embeds.reshape(B * T, d), B, T, attention_mask, max_new, beams=num_beams, right_pad_fix=fix)
         state = {"first": True}
 
         def step_fn(tokens, src_rows):

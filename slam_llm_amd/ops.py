@@ -649,11 +649,12 @@ def attn_bwd(q2d, k2d, v2d, o2d, do2d, lse, dq2d, dk2d, dv2d, B, T, Hq, Hkv, D, 
 
 
 def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors,
-                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None, qk_norm=None):
+                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None, qk_norm=None, prompt_end=None):
     """one decode step of attention per hypothesis: (q|k|v bias +) LoRA delta + RoPE + KV append of the new token, then one
     query per row against [prompt KV of its batch item | generated KV via the ancestor table].  qkv_bias: fp32
     [(Hq + 2 Hkv) D] (Qwen2) or None.  qk_norm: (q_weight, k_weight, eps), fp32 [D] each (Qwen3: per-head RMSNorm of the new q / k
-    behind bias and LoRA delta, before RoPE) or None."""
+    behind bias and LoRA delta, before RoPE) or None.  prompt_end: int32 [B] or None; given, the prompt keys of item b are the slots
+    [prompt_start[b], prompt_end[b]) of its block (right-padded batches) and the call goes through slam_attn_decode_span."""
     R, G = k_gen.shape[0], k_gen.shape[1]
     Tp = k_prompt.shape[1]
     args = (_p(qkv), _ld(qkv), _p(lora_b), _ld(lora_b) if lora_b is not None else 0, lora_r, _p(cos), _p(sin), _p(positions),
@@ -664,6 +665,11 @@ def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, pr
     if qk_norm is not None:
         _norm_w(qk_norm[0], Hq, D, "attn_decode")
         _norm_w(qk_norm[1], Hkv, D, "attn_decode")
+    if prompt_end is not None:
+        assert prompt_end.dtype == torch.int32 and prompt_start is not None and prompt_end.shape == prompt_start.shape
+        qn = qk_norm if qk_norm is not None else (None, None, 0.0)
+        fn = lambda: call("slam_attn_decode_span", *args, _p(qkv_bias), _p(qn[0]), _p(qn[1]), float(qn[2]), _p(prompt_end), _s())  # noqa: E731
+    elif qk_norm is not None:
         fn = lambda: call("slam_attn_decode_qknorm", *args, _p(qkv_bias), _p(qk_norm[0]), _p(qk_norm[1]), float(qk_norm[2]), _s())  # noqa: E731
     elif qkv_bias is None:
         fn = lambda: call("slam_attn_decode", *args, _s())  # noqa: E731

@@ -211,6 +211,10 @@ def build_config(train_config, model_config) -> dict:
                  # HuBERT + Q-Former on ragged batches: the reference forwards fairseq's padding mask un-inverted;
                  # default = reference behaviour, true = attend to the real frames
                  hubert_qformer_mask_fix=bool(_get(model_config, "hubert_qformer_mask_fix", False)),
+                 # generate() on right-padded prompt batches (MultiTaskDataset.collator): the reference takes the first token from the pad
+                 # query at the last slot and restarts the new positions at 1; default = reference behaviour, true = every
+                 # row decodes as if alone and unpadded.  generate(..., generate_right_pad_fix=...) overrides it per call
+                 generate_right_pad_fix=bool(_get(model_config, "generate_right_pad_fix", False)),
                  # train_config.freeze_encoder=false: the (Whisper) encoder trains with the projector and the adapters
                  freeze_encoder=bool(_get(train_config, "freeze_encoder", True)))
     if enc_name == "hubert":
