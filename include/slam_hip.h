@@ -481,6 +481,28 @@ int slam_head_rmsnorm_rope(void* qkv, int64_t ld, int64_t col0, const float* q_w
 int slam_head_rmsnorm_bwd(void* dqkv, int64_t ld, int64_t col0, const void* x, const float* rstd, const float* q_weight,
                           const float* k_weight, int64_t M, int64_t Hq, int64_t Hkv, int64_t D, void* stream);
 
+/* slam_attn_decode_span with partial rotary embedding (HF Phi3ForCausalLM, partial_rotary_factor < 1): only the first rot_dim dims
+ * of every q / k head rotate, pair (i, i + rot_dim/2); dims [rot_dim, D) pass through.  The tables stay [P, D/2] fp32: columns
+ * [0, rot_dim/2) hold cos / sin (times the attention factor of longrope), columns [rot_dim/2, D/2) hold 1 and 0.  rot_dim: a multiple
+ * of 16 in [16, D]; rot_dim = D is slam_attn_decode_span bit for bit.  The q/k norm weights must be null when rot_dim < D. */
+int slam_attn_decode_partial(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                             const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt,
+                             const void* v_prompt, const int32_t* prompt_start, void* k_gen, void* v_gen, int32_t* ancestors,
+                             const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R, int64_t beams,
+                             int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, const float* qkv_bias,
+                             const float* q_norm_w, const float* k_norm_w, float eps, const int32_t* prompt_end, int64_t rot_dim,
+                             void* stream);
+
+/* Partial rotary embedding in place on the H adjacent heads at columns [col0, col0 + H*D) of src [B*T, ld] bf16 (HF
+ * apply_rotary_pos_emb with rotary_dim = rot_dim < D): y[i] = x[i] c[i] - x[i + rot_dim/2] s[i], y[i + rot_dim/2] = x[i + rot_dim/2] c[i]
+ * + x[i] s[i] for i < rot_dim/2, one bf16 rounding of the fp32 result; dims [rot_dim, D) are neither read nor written.  cos / sin:
+ * [P, D/2] fp32 tables of which columns [0, rot_dim/2) are read; positions: [B*T] int32 table row, or null for position = t.
+ * inverse != 0 applies the transposed rotation (sin negated): the adjoint, also when the tables carry an attention factor.  No
+ * transposed copy is written.  rot_dim: a multiple of 16 in [16, D] (at rot_dim = D the result equals slam_head_rope_transpose's
+ * in-place rotation bit for bit); D in {64, 128}. */
+int slam_head_rope_partial(void* src, int64_t ld, int64_t col0, const float* cos_table, const float* sin_table, int inverse,
+                           int64_t B, int64_t T, int64_t H, int64_t D, int64_t rot_dim, const int32_t* positions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,7 @@ struct DecodeAttnParams {
   const float* bias;               // [(Hq+2Hkv)*D] fp32 q|k|v projection bias (Qwen2) or null
   const float* qnorm; const float* knorm; float norm_eps;  // [D] fp32 per-head RMSNorm weights of q and k (Qwen3) or null
   const float* cosT; const float* sinT; const int* positions;  // RoPE tables [P, D/2], position per row
+  int rot;                         // rotary dims of a head (partial rotary: pairs (i, i + rot/2), dims [rot, D) pass through); D = all
   const bf16_t* Kp; const bf16_t* Vp;  // prompt KV [B, Tp, Hkv*D]
   const int* start;                // [B] first valid prompt slot (left padding), null = 0
   const int* end;                  // [B] one past the last valid prompt slot (right padding), null = Tp
@@ -401,17 +402,21 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
     const int pos = p.positions[r];
     for (int idx = tid; idx < NH * (D / 2); idx += NW * 64) {
       const int hh = idx / (D / 2), d = idx % (D / 2);
+      // the two elements of pair d: (d, d + rot/2) inside the rotary dims, (d + rot/2, d + D/2) behind them, where the tables hold
+      // cos = 1, sin = 0 and the rotation below returns its inputs; rot = D gives (d, d + D/2) for every d.  rot is wave-uniform
+      const int hr = p.rot >> 1;
+      const int e1 = d + (d < hr ? 0 : hr), e2 = d + (d < hr ? hr : D / 2);
       // column of head hh in the fused q|k|v output
       const int col = hh < REP ? (hk * REP + hh) * D : (hh == REP ? QD + hk * D : QD + KD + hk * D);
-      float x1 = bf2f(row[col + d]), x2 = bf2f(row[col + D / 2 + d]);
+      float x1 = bf2f(row[col + e1]), x2 = bf2f(row[col + e2]);
       if (p.bias) {     // Linear with bias (HF): x W^T + b in fp32, one bf16 rounding, before the LoRA delta and RoPE
-        x1 = bf2f(f2bf(x1 + p.bias[col + d]));
-        x2 = bf2f(f2bf(x2 + p.bias[col + D / 2 + d]));
+        x1 = bf2f(f2bf(x1 + p.bias[col + e1]));
+        x2 = bf2f(f2bf(x2 + p.bias[col + e2]));
       }
       if (p.lora_b) {   // peft: result = base(x) + scale * B(A(x)), both terms rounded to bf16 before the add
         const bf16_t* u = row + QD + 2 * KD;
-        const bf16_t* b1 = p.lora_b + (int64_t)(col + d) * p.ldlb;
-        const bf16_t* b2 = p.lora_b + (int64_t)(col + D / 2 + d) * p.ldlb;
+        const bf16_t* b1 = p.lora_b + (int64_t)(col + e1) * p.ldlb;
+        const bf16_t* b2 = p.lora_b + (int64_t)(col + e2) * p.ldlb;
         float d1 = 0.f, d2 = 0.f;
         int j = 0;
         if ((p.ldlb & 7) == 0 && (p.ld & 7) == 0) {  // 16-byte aligned rows: 8 ranks per load
@@ -443,8 +448,8 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
         for (int o = D / 4; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
         const float rstd = rsqrtf(ss / (float)D + p.norm_eps);
         const float* w = hh < REP ? p.qnorm : p.knorm;
-        x1 = bf2f(f2bf(w[d] * bf2f(f2bf(x1 * rstd))));   // Qwen3RMSNorm: cast back to bf16, then the weight
-        x2 = bf2f(f2bf(w[D / 2 + d] * bf2f(f2bf(x2 * rstd))));
+        x1 = bf2f(f2bf(w[e1] * bf2f(f2bf(x1 * rstd))));   // Qwen3RMSNorm: cast back to bf16, then the weight
+        x2 = bf2f(f2bf(w[e2] * bf2f(f2bf(x2 * rstd))));
       }
       if (hh <= REP) {  // q heads and k: rotate (HF rotate_half convention), round to bf16 like the prefill path
         const float cs = p.cosT[(int64_t)pos * (D / 2) + d], sn = p.sinT[(int64_t)pos * (D / 2) + d];
@@ -454,11 +459,11 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeAttnParams p) {
       }
       if (hh >= REP) {
         bf16_t* dst = (hh == REP ? p.Kg : p.Vg) + ((int64_t)r * p.G + n_prev) * HD + hk * D;
-        dst[d] = f2bf(x1);
-        dst[D / 2 + d] = f2bf(x2);
+        dst[e1] = f2bf(x1);
+        dst[e2] = f2bf(x2);
       }
-      tok[hh][d] = f2bf(x1);
-      tok[hh][D / 2 + d] = f2bf(x2);
+      tok[hh][e1] = f2bf(x1);
+      tok[hh][e2] = f2bf(x2);
     }
   }
   __syncthreads();
@@ -622,7 +627,7 @@ static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const v
                             const float* qkv_bias, const float* q_norm_w, const float* k_norm_w, float norm_eps,
                             const float* cos_table, const float* sin_table, const int32_t* positions, const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, const int32_t* prompt_end, void* k_gen, void* v_gen,
                             int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count, void* O, int64_t ldo, int64_t R,
-                            int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, void* stream) {
+                            int64_t beams, int64_t Tp, int64_t G, int64_t Hq, int64_t Hkv, int64_t D, float scale, int64_t rot_dim, void* stream) {
   SLAM_CHECK_ARG(qkv && cos_table && sin_table && positions && k_prompt && v_prompt && k_gen && v_gen && ancestors && O,
                  "%s: null pointer", fn);
   SLAM_CHECK_ARG(D == 64 || D == 128, "%s: head_dim must be 64 or 128 (got %lld)", fn, (long long)D);
@@ -632,11 +637,14 @@ static int attn_decode_impl(const char* fn, const void* qkv, int64_t ld, const v
   SLAM_CHECK_ARG(Hkv > 0 && Hq % Hkv == 0, "%s: Hq must be a multiple of Hkv", fn);
   SLAM_CHECK_ARG(!lora_b || (lora_r > 0 && ldlb >= lora_r), "%s: bad LoRA block", fn);
   SLAM_CHECK_ARG((q_norm_w == nullptr) == (k_norm_w == nullptr), "%s: q/k norm weights must both be set or both null", fn);
+  SLAM_CHECK_ARG(rot_dim >= 16 && rot_dim <= D && rot_dim % 16 == 0, "%s: rot_dim %lld must be a multiple of 16 in [16, head_dim]", fn,
+                 (long long)rot_dim);
+  SLAM_CHECK_ARG(!q_norm_w || rot_dim == D, "%s: per-head q/k norm with partial rotary (rot_dim < head_dim) is not implemented", fn);
   DecodeAttnParams p;
   p.qkv = (const bf16_t*)qkv; p.ld = ld; p.lora_b = (const bf16_t*)lora_b; p.ldlb = ldlb; p.lora_r = (int)lora_r;
   p.bias = qkv_bias;
   p.qnorm = q_norm_w; p.knorm = k_norm_w; p.norm_eps = norm_eps;
-  p.cosT = cos_table; p.sinT = sin_table; p.positions = positions;
+  p.cosT = cos_table; p.sinT = sin_table; p.positions = positions; p.rot = (int)rot_dim;
   p.Kp = (const bf16_t*)k_prompt; p.Vp = (const bf16_t*)v_prompt; p.start = prompt_start; p.end = prompt_end;
   p.Kg = (bf16_t*)k_gen; p.Vg = (bf16_t*)v_gen; p.anc = ancestors;
   p.gen_count_dev = gen_count_dev; p.gen_count_host = (int)gen_count; p.O = (bf16_t*)O; p.ldo = ldo;
@@ -657,7 +665,7 @@ extern "C" int slam_attn_decode(const void* qkv, int64_t ld, const void* lora_b,
                                 int64_t D, float scale, void* stream) {
   return attn_decode_impl("slam_attn_decode", qkv, ld, lora_b, ldlb, lora_r, nullptr, nullptr, nullptr, 0.f, cos_table, sin_table, positions,
                           k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O, ldo, R,
-                          beams, Tp, G, Hq, Hkv, D, scale, stream);
+                          beams, Tp, G, Hq, Hkv, D, scale, D, stream);
 }
 
 extern "C" int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
@@ -668,7 +676,7 @@ extern "C" int slam_attn_decode_bias(const void* qkv, int64_t ld, const void* lo
                                      int64_t Hkv, int64_t D, float scale, const float* qkv_bias, void* stream) {
   return attn_decode_impl("slam_attn_decode_bias", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, nullptr, nullptr, 0.f, cos_table,
                           sin_table, positions, k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count, O,
-                          ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
+                          ldo, R, beams, Tp, G, Hq, Hkv, D, scale, D, stream);
 }
 
 /* slam_attn_decode_bias plus the per-head RMSNorm of q and k (HF Qwen3Attention.forward: q_norm / k_norm, Qwen3RMSNorm.forward). */
@@ -681,7 +689,7 @@ extern "C" int slam_attn_decode_qknorm(const void* qkv, int64_t ld, const void* 
                                        const float* k_norm_w, float eps, void* stream) {
   return attn_decode_impl("slam_attn_decode_qknorm", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
                           sin_table, positions, k_prompt, v_prompt, prompt_start, nullptr, k_gen, v_gen, ancestors, gen_count_dev, gen_count,
-                          O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
+                          O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, D, stream);
 }
 /* slam_attn_decode_qknorm over a prompt span per item: keys [prompt_start[item], prompt_end[item]) of the prompt block (right-padded
  * batches); a null prompt_end means Tp. */
@@ -694,5 +702,21 @@ extern "C" int slam_attn_decode_span(const void* qkv, int64_t ld, const void* lo
                                      const float* k_norm_w, float eps, const int32_t* prompt_end, void* stream) {
   return attn_decode_impl("slam_attn_decode_span", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
                           sin_table, positions, k_prompt, v_prompt, prompt_start, prompt_end, k_gen, v_gen, ancestors, gen_count_dev,
-                          gen_count, O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, stream);
+                          gen_count, O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, D, stream);
+}
+
+/* slam_attn_decode_span with partial rotary embedding (HF Phi3: partial_rotary_factor < 1): only the first rot_dim dims of a q / k head
+ * rotate, pair (i, i + rot_dim/2); the tables stay [P, D/2] with cos = 1, sin = 0 in columns [rot_dim/2, D/2).  rot_dim = D is
+ * slam_attn_decode_span, bit for bit. */
+extern "C" int slam_attn_decode_partial(const void* qkv, int64_t ld, const void* lora_b, int64_t ldlb, int64_t lora_r,
+                                        const float* cos_table, const float* sin_table, const int32_t* positions,
+                                        const void* k_prompt, const void* v_prompt, const int32_t* prompt_start, void* k_gen,
+                                        void* v_gen, int32_t* ancestors, const int32_t* gen_count_dev, int64_t gen_count,
+                                        void* O, int64_t ldo, int64_t R, int64_t beams, int64_t Tp, int64_t G, int64_t Hq,
+                                        int64_t Hkv, int64_t D, float scale, const float* qkv_bias, const float* q_norm_w,
+                                        const float* k_norm_w, float eps, const int32_t* prompt_end, int64_t rot_dim,
+                                        void* stream) {
+  return attn_decode_impl("slam_attn_decode_partial", qkv, ld, lora_b, ldlb, lora_r, qkv_bias, q_norm_w, k_norm_w, eps, cos_table,
+                          sin_table, positions, k_prompt, v_prompt, prompt_start, prompt_end, k_gen, v_gen, ancestors, gen_count_dev,
+                          gen_count, O, ldo, R, beams, Tp, G, Hq, Hkv, D, scale, rot_dim, stream);
 }

@@ -97,6 +97,51 @@ __global__ __launch_bounds__(256) void head_rope_transpose_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
+// partial rotary embedding (HF apply_rotary_pos_emb with partial_rotary_factor < 1: Phi-3 / Phi-4), in place, no transposed
+// copy.  Only the first `rot` dims of a head rotate, pair (i, i + rot/2); dims [rot, D) are never read or written.  One
+// lane owns 8 pairs: 16 bytes at i and 16 bytes at i + rot/2 (rot % 16 == 0 keeps both chunks aligned); the lanes whose
+// chunk lies at or past rot/2 pairs have nothing to do.  blockIdx.y = head, 256 / (D/16) rows per block.  The arithmetic is
+// head_rope_transpose_kernel's, expression for expression: at rot = D the two kernels write the same bits.
+// ------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void head_rope_partial_kernel(
+    bf16_t* __restrict__ src, int64_t ld, int col0, const float* __restrict__ cosT, const float* __restrict__ sinT,
+    float sin_sign, int64_t M, int T, int rot, const int* __restrict__ positions) {
+  constexpr int HC = D / 16;          // 16-byte chunks in half a head
+  constexpr int ROWS = 256 / HC;      // rows per block
+  const int c = threadIdx.x % HC;
+  const int64_t row = (int64_t)blockIdx.x * ROWS + threadIdx.x / HC;
+  if (row >= M || c * 16 >= rot) return;
+  bf16_t* p = src + row * ld + col0 + (int)blockIdx.y * D;
+  const u16x8_t x1 = *reinterpret_cast<const u16x8_t*>(p + c * 8);
+  const u16x8_t x2 = *reinterpret_cast<const u16x8_t*>(p + rot / 2 + c * 8);
+  const int pp = positions ? positions[row] : (int)(row % T);
+  const float* cp = cosT + (int64_t)pp * (D / 2) + c * 8;
+  const float* sp = sinT + (int64_t)pp * (D / 2) + c * 8;
+  const float4 c0 = *reinterpret_cast<const float4*>(cp), c1 = *reinterpret_cast<const float4*>(cp + 4);
+  const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+  const float cs8[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float sn8[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+  float r1[8], r2[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const float cs = cs8[e], sn = sn8[e] * sin_sign;
+    const float a = bf2f(x1[e]), bb = bf2f(x2[e]);
+    r1[e] = a * cs - bb * sn;
+    r2[e] = bb * cs + a * sn;
+  }
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+  u32x4_t w1, w2;
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    w1[e] = pack2bf(r1[2 * e], r1[2 * e + 1]);
+    w2[e] = pack2bf(r2[2 * e], r2[2 * e + 1]);
+  }
+  *reinterpret_cast<u16x8_t*>(p + c * 8) = __builtin_bit_cast(u16x8_t, w1);
+  *reinterpret_cast<u16x8_t*>(p + rot / 2 + c * 8) = __builtin_bit_cast(u16x8_t, w2);
+}
+
+// ------------------------------------------------------------------------------------------
 // generic transpose: in [R, C] (ld) -> out [C, Rp] (ldo), rows R..Rp-1 written as zeros
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict__ in, int64_t ldi,
@@ -1002,6 +1047,30 @@ extern "C" int slam_head_rope_transpose(void* src, int64_t ld, int64_t col0, con
     hipLaunchKernelGGL(head_rope_transpose_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream,
                        (bf16_t*)src, ld, (int)col0, cos_table, sin_table, sgn, (bf16_t*)dstT, (int)T, (int)Tp, (int)H, positions);
   SLAM_CHECK_LAUNCH("slam_head_rope_transpose");
+  return 0;
+}
+
+extern "C" int slam_head_rope_partial(void* src, int64_t ld, int64_t col0, const float* cos_table, const float* sin_table,
+                                      int inverse, int64_t B, int64_t T, int64_t H, int64_t D, int64_t rot_dim,
+                                      const int32_t* positions, void* stream) {
+  SLAM_CHECK_ARG(src && cos_table && sin_table, "slam_head_rope_partial: null pointer");
+  SLAM_CHECK_ARG(D == 64 || D == 128, "slam_head_rope_partial: head_dim %ld unsupported (64|128)", (long)D);
+  SLAM_CHECK_ARG(rot_dim >= 16 && rot_dim <= D && rot_dim % 16 == 0,
+                 "slam_head_rope_partial: rot_dim %ld must be a multiple of 16 in [16, head_dim]", (long)rot_dim);
+  SLAM_CHECK_ARG(B > 0 && T > 0 && H > 0 && H <= 65535, "slam_head_rope_partial: bad shape");
+  SLAM_CHECK_ARG(ld % 8 == 0 && col0 % 8 == 0 && col0 >= 0 && col0 + H * D <= ld,
+                 "slam_head_rope_partial: ld/col0 must be multiples of 8 and the heads must lie inside the row");
+  const int64_t M = B * T;
+  const int rows = 256 / (int)(D / 16);
+  dim3 grid((unsigned)cdiv64(M, rows), (unsigned)H);
+  const float sgn = inverse ? -1.f : 1.f;
+  if (D == 64)
+    hipLaunchKernelGGL(head_rope_partial_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)src, ld, (int)col0,
+                       cos_table, sin_table, sgn, M, (int)T, (int)rot_dim, positions);
+  else
+    hipLaunchKernelGGL(head_rope_partial_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)src, ld, (int)col0,
+                       cos_table, sin_table, sgn, M, (int)T, (int)rot_dim, positions);
+  SLAM_CHECK_LAUNCH("slam_head_rope_partial");
   return 0;
 }
 

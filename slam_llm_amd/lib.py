@@ -97,6 +97,9 @@ SIGNATURES = {
                                 I64, F, P, P, P, F, P],
     "slam_attn_decode_span": [P, I64, P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, I64,
                               I64, F, P, P, P, F, P, P],
+    "slam_attn_decode_partial": [P, I64, P, I64, I64, P, P, P, P, P, P, P, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, I64,
+                                 I64, F, P, P, P, F, P, I64, P],
+    "slam_head_rope_partial": [P, I64, I64, P, P, I32, I64, I64, I64, I64, I64, P, P],
     "slam_head_rmsnorm_rope": [P, I64, I64, P, P, F, P, P, P, P, P, I64, I64, I64, I64, I64, P],
     "slam_head_rmsnorm_bwd": [P, I64, I64, P, P, P, P, I64, I64, I64, I64, P],
     "slam_embed_splice_fwd": [P, P, P, I64, P, I64, P, I64, P, I64, I64, I64, I64, P],

@@ -147,6 +147,7 @@ def make_config(encoder: Optional[str] = None, llm: Optional[str] = None, **kw) 
     cfg = dict(n_mels=80, enc_dim=128, enc_heads=2, enc_layers=2, enc_ctx=1500, ds_rate=5, proj_hidden=2048,
                llm_dim=128, llm_layers=2, llm_heads=2, llm_kv_heads=1, llm_head_dim=64, llm_ffn=256, vocab=512,
                rope_theta=10000.0, rms_eps=1e-5, llm_qkv_bias=False, tie_embeddings=False, llm_qk_norm=False, rope_scaling=None,
+               llm_fused_proj=False, llm_rotary_dim=None, llm_sliding_window=None,
                lora_r=8, lora_alpha=32, lora_targets=("q_proj", "v_proj"), lora_dropout=0.0)
     if encoder:
         cfg.update(PRESETS[encoder])
@@ -272,7 +273,7 @@ class FusedLinear:
         # a frozen [gate ; up] group without adapters also keeps its rows block-interleaved for the fused SwiGLU-forward product
         # (288 GB: a third copy of these 235 MB per Llama-3-8B layer is free; the decode / eval paths keep using Wext)
         self.Wil = None
-        if FUSE_SWIGLU_FWD and [n for n, _ in self.parts] == ["gate_proj", "up_proj"] and not self.adapters and (self.N // 2) % 64 == 0:
+        if FUSE_SWIGLU_FWD and [n for n, _ in self.parts] in (["gate_proj", "up_proj"], ["gate_up_proj"]) and not self.adapters and (self.N // 2) % 64 == 0:
             self.Wil = ops.interleave_gate_up(self.Wext)
 
     def refresh(self, store: TrainableStore):
@@ -2177,9 +2178,16 @@ class HipLlamaLora(nn.Module):
     cfg['tie_embeddings'] (lm_head IS the input embedding).  Qwen3 (HF Qwen3ForCausalLM) adds cfg['llm_qk_norm']: a frozen RMSNorm
     over head_dim on every q and k head between the projection (+ LoRA delta) and RoPE, one fused launch with the RoPE in the training
     forward and prefill, one launch in the backward, inside the attention kernel in decode.  cfg['rope_scaling'] (None or an HF
-    rope_scaling dict of type llama3 / linear) only changes the cos/sin tables."""
+    rope_scaling dict of type llama3 / linear) only changes the cos/sin tables.  Phi-3 / Phi-4 (HF Phi3ForCausalLM): cfg['llm_fused_proj']
+    names the two input groups as the checkpoint and peft do -- ONE Linear qkv_proj (rows [q; k; v]) and ONE gate_up_proj (rows
+    [gate; up]), each with one adapter over all its rows -- which is the row order these groups already run in;
+    cfg['llm_rotary_dim'] < head_dim rotates only the first dims of a head (tables with cos = 1, sin = 0 behind them; a stand-alone
+    elementwise launch in the forward, prefill and -- with null tables to the attention backward -- as the adjoint on dq | dk; inside
+    the attention kernel in decode); rope_scaling of type longrope scales the frequencies per dim and cos / sin by an attention factor;
+    cfg['llm_sliding_window'] must cover every sequence."""
 
-    ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
+    ATTN = ("q_proj", "k_proj", "v_proj", "o_proj", "qkv_proj")
+    FUSED_TARGETS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
 
     def __init__(self, cfg: dict, store: TrainableStore, device, prefix="llm."):
         super().__init__()
@@ -2197,16 +2205,31 @@ class HipLlamaLora(nn.Module):
         self.qkv_bias = bool(cfg.get("llm_qkv_bias", False))
         self.tied = bool(cfg.get("tie_embeddings", False))
         self.qk_norm = bool(cfg.get("llm_qk_norm", False))
+        self.fused_proj = bool(cfg.get("llm_fused_proj", False))
+        self.rot_dim = int(cfg.get("llm_rotary_dim") or D)      # rotary dims of a head; < D: partial rotary
+        self.window = cfg.get("llm_sliding_window") or None
+        if self.rot_dim != D and (self.rot_dim % 16 != 0 or not 16 <= self.rot_dim < D):
+            raise NotImplementedError(f"llm_rotary_dim {self.rot_dim} must be a multiple of 16 in [16, head_dim {D}]")
+        if self.qk_norm and self.rot_dim != D:
+            raise NotImplementedError("llm_qk_norm together with partial rotary (llm_rotary_dim < llm_head_dim) is not implemented")
         targets = tuple(cfg.get("lora_targets") or ())
+        if self.fused_proj and any(t not in self.FUSED_TARGETS for t in targets):
+            # peft finds no such module in a Phi3 decoder either (its Linears are qkv_proj, o_proj, gate_up_proj, down_proj)
+            raise ValueError(f"lora_targets {[t for t in targets if t not in self.FUSED_TARGETS]} name no Linear of a fused-projection "
+                             f"(Phi3) decoder; valid targets: {list(self.FUSED_TARGETS)}")
         r, alpha = cfg["lora_r"], cfg["lora_alpha"]
         P = prefix + "base_model.model."
         # reserve in backward-production order: last layer first
         for i in reversed(range(cfg["llm_layers"])):
             # bias: fp32 [(Hq + 2 Hkv) D] q|k|v bias (Qwen2) or None; q_norm / k_norm: fp32 [D] per-head RMSNorm weights (Qwen3) or None
             L = SimpleNamespace(bias=None, q_norm=None, k_norm=None)
-            L.qkv = FusedLinear(d, [("q_proj", Hq * D), ("k_proj", Hkv * D), ("v_proj", Hkv * D)], device)
+            if self.fused_proj:
+                L.qkv = FusedLinear(d, [("qkv_proj", (Hq + 2 * Hkv) * D)], device)
+                L.gu = FusedLinear(d, [("gate_up_proj", 2 * Fd)], device)
+            else:
+                L.qkv = FusedLinear(d, [("q_proj", Hq * D), ("k_proj", Hkv * D), ("v_proj", Hkv * D)], device)
+                L.gu = FusedLinear(d, [("gate_proj", Fd), ("up_proj", Fd)], device)
             L.o = FusedLinear(Hq * D, [("o_proj", d)], device)
-            L.gu = FusedLinear(d, [("gate_proj", Fd), ("up_proj", Fd)], device)
             L.down = FusedLinear(Fd, [("down_proj", d)], device)
             for fl in (L.down, L.gu, L.o, L.qkv):
                 mine = [(n, rows) for n, rows in fl.parts if n in targets]
@@ -2307,9 +2330,24 @@ class HipLlamaLora(nn.Module):
     def rope(self, T: int):
         if T not in self._rope:
             from .host_tables import rope_tables
-            cos, sin = rope_tables(T, self.cfg["llm_head_dim"], self.cfg["rope_theta"], self.cfg.get("rope_scaling"))
+            cos, sin = rope_tables(T, self.cfg["llm_head_dim"], self.cfg["rope_theta"], self.cfg.get("rope_scaling"),
+                                   rot_dim=self.rot_dim if self.rot_dim != self.cfg["llm_head_dim"] else None)
             self._rope[T] = (cos.to(self.device_), sin.to(self.device_))
         return self._rope[T]
+
+    def _check_window(self, length: int, what: str):
+        """HF's sliding-window mask equals the causal mask while no sequence is longer than the window; nothing else is implemented"""
+        if self.window is not None and length > self.window:
+            raise NotImplementedError(f"{what} spans {length} positions, beyond llm_sliding_window={self.window}: sliding-window attention "
+                                      "is only implemented up to the window (where it equals causal attention)")
+
+    def _check_longrope(self, length: int):
+        """HF switches from short_factor to long_factor once the sequence outgrows the pretrained length, over a prefix cached under the
+        other frequencies; generate() does not reproduce that"""
+        sc = self.cfg.get("rope_scaling") or {}
+        if sc.get("rope_type") == "longrope" and length > sc["original_max_position_embeddings"]:
+            raise NotImplementedError(f"generate(): prompt + max_new_tokens = {length} exceeds the longrope original_max_position_embeddings="
+                                      f"{sc['original_max_position_embeddings']} (HF changes frequencies mid-sequence there; not implemented)")
 
     # ---- forward -------------------------------------------------------------------------------------
     def forward_hip(self, h: torch.Tensor, B: int, T: int, key_mask: torch.Tensor, targets, n_valid,
@@ -2321,6 +2359,7 @@ class HipLlamaLora(nn.Module):
                                 cfg["llm_ffn"], cfg["vocab"])
         M = B * T
         eps = cfg["rms_eps"]
+        self._check_window(packed[3] if packed is not None else T, "the forward")
         # packed = (positions, seg_lo, seg_hi, max_len): B = 1, sequences concatenated along T without pad tokens
         positions, seg = (packed[0], (packed[1], packed[2])) if packed is not None else (None, None)
         cos, sin = self.rope(packed[3] if packed is not None else T)
@@ -2365,7 +2404,7 @@ class HipLlamaLora(nn.Module):
                 qk_rstd, qk_x = ops.head_rmsnorm_rope(qkv, 0, B, T, Hq, Hkv, D, L.q_norm, L.k_norm, eps, cos, sin, positions=positions,
                                                       stash=train)
             else:
-                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)     # q and k heads: adjacent columns, one launch
+                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions, rot_dim=self.rot_dim)     # q and k heads: adjacent columns, one launch
             o_ext = L.o.new_input(M)
             _, lse = ops.attn_fwd(qkv[:, : Hq * D], qkv[:, Hq * D: (Hq + Hkv) * D], qkv[:, (Hq + Hkv) * D:], B, T, Hq, Hkv, D, True, scale,
                                   key_mask=key_mask, want_lse=train, out=o_ext[:, : Hq * D], seg=seg)
@@ -2471,6 +2510,8 @@ class HipLlamaLora(nn.Module):
                            "++model_config.generate_right_pad_fix=true (or generate(..., generate_right_pad_fix=True)) to decode every "
                            "row as if it were alone and unpadded.")
         positions = sp.positions
+        self._check_window(T + G, "generate() (prompt + max_new_tokens)")
+        self._check_longrope(T + G)
         cos, sin = self.rope(T + G)
         Tp64 = round_up(T, 64)
         key_mask = torch.zeros((B, Tp64), dtype=torch.uint8, device=dev)
@@ -2492,7 +2533,7 @@ class HipLlamaLora(nn.Module):
             if self.qk_norm:
                 ops.head_rmsnorm_rope(qkv, 0, B, T, Hq, Hkv, D, L.q_norm, L.k_norm, eps, cos, sin, positions=positions)
             else:
-                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions)
+                ops.rope_inplace(qkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=positions, rot_dim=self.rot_dim)
             cache.Kp[li].copy_(qkv[:, Hq * D:(Hq + Hkv) * D].view(B, T, Hkv * D))
             cache.Vp[li].copy_(qkv[:, (Hq + Hkv) * D:].view(B, T, Hkv * D))
             o_ext = L.o.new_input(M)
@@ -2536,7 +2577,7 @@ class HipLlamaLora(nn.Module):
             ops.attn_decode(qkv, lora_b, lora_r, cos, sin, cache.next_pos, cache.Kp[li], cache.Vp[li], cache.start,
                             cache.Kg[li], cache.Vg[li], cache.anc, cache.n_dev, cache.n, cache.beams, Hq, Hkv, D,
                             D ** -0.5, o_ext, qkv_bias=L.bias, qk_norm=(L.q_norm, L.k_norm, eps) if self.qk_norm else None,
-                            prompt_end=cache.end)
+                            prompt_end=cache.end, rot_dim=self.rot_dim)
             h_mid = L.o.forward(o_ext, st, residual=h)
             x2 = L.gu.new_input(R)
             ops.rmsnorm_fwd(h_mid, L.ln2, eps, out=x2[:, :d])
@@ -2580,6 +2621,9 @@ class HipLlamaLora(nn.Module):
         packed = stash.get("packed")
         cos, sin = self.rope(packed[3] if packed is not None else T)
         rope = (cos, sin, packed[0]) if packed is not None else (cos, sin)
+        partial = self.rot_dim != D
+        if partial:     # the attention backward's fused adjoint pairs (d, d + D/2): it gets no tables, the adjoint is a launch of its own
+            rope = None
         seg = (packed[1], packed[2]) if packed is not None else None
         scale = D ** -0.5
         f = stash.pop("final")
@@ -2646,6 +2690,9 @@ class HipLlamaLora(nn.Module):
                          dqkv[:, : Hq * D], dqkv[:, Hq * D: (Hq + Hkv) * D], dqkv[:, (Hq + Hkv) * D:],
                          B, T, Hq, Hkv, D, True, scale, key_mask=key_mask, rope=rope, seg=seg)  # RoPE backward fused
             del do_ext, dO
+            if partial:     # dq | dk w.r.t. the rotated heads -> w.r.t. the projection's output: the transposed rotation, same (scaled) tables
+                ops.rope_inplace(dqkv, 0, B, T, Hq + Hkv, D, cos, sin, positions=packed[0] if packed is not None else None, inverse=True,
+                                 rot_dim=self.rot_dim)
             if self.qk_norm:    # dq / dk are gradients w.r.t. the normed, un-rotated heads: through the per-head RMSNorm, in place
                 ops.head_rmsnorm_bwd(dqkv, 0, S["qk_x"], S["qk_rstd"], Hq, Hkv, D, L.q_norm, L.k_norm)
             dx1 = L.qkv.backward(dqkv, S["x1"], st, accumulate, drop=dq_, defer=dfr)

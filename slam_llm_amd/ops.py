@@ -456,11 +456,30 @@ def transpose(x2d, Rp=None, out=None):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def rope_inplace(src2d, col0, B, T, H, D, cos, sin, positions=None, inverse=False):
+def rope_inplace(src2d, col0, B, T, H, D, cos, sin, positions=None, inverse=False, rot_dim=None):
     """HF apply_rotary_pos_emb on columns [col0, col0 + H*D) of src2d [B*T, ld], in place (q and k heads are adjacent columns of the fused
     QKV buffer: one launch with H = Hq + Hkv rotates both).  No transposed copy is written: the attention kernels read their transposed
-    operands from the row-major tiles (ds_read_b64_tr_b16)."""
-    head_rope_transpose(src2d, col0, B, T, H, D, cos=cos, sin=sin, inverse=inverse, want_t=False, positions=positions)
+    operands from the row-major tiles (ds_read_b64_tr_b16).  rot_dim < D (Phi-3 / Phi-4 partial rotary): only the first rot_dim dims of
+    a head rotate, pair (i, i + rot_dim/2), through slam_head_rope_partial; inverse=True is the transposed rotation (the adjoint)."""
+    if rot_dim is None or rot_dim == D:
+        head_rope_transpose(src2d, col0, B, T, H, D, cos=cos, sin=sin, inverse=inverse, want_t=False, positions=positions)
+    else:
+        head_rope_partial(src2d, col0, B, T, H, D, rot_dim, cos, sin, positions=positions, inverse=inverse)
+
+
+def head_rope_partial(src2d, col0, B, T, H, D, rot_dim, cos, sin, positions=None, inverse=False):
+    """slam_head_rope_partial: rotary embedding over the first rot_dim dims of H adjacent heads, in place; rot_dim a multiple of 16 in
+    [16, D] (rot_dim = D writes what rope_inplace writes).  cos / sin: [P, D/2] fp32, columns [0, rot_dim/2) are read."""
+    M = B * T
+    assert src2d.dtype == torch.bfloat16 and src2d.shape[0] == M
+    assert cos is not None and sin is not None and cos.dtype == torch.float32 and sin.dtype == torch.float32
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.shape == sin.shape and cos.dim() == 2 and cos.shape[1] == D // 2
+    assert positions is not None or cos.shape[0] >= T
+    assert positions is None or (positions.dtype == torch.int32 and positions.is_contiguous() and positions.numel() == M)
+    _timed("head_rope_partial", 0.0,
+           lambda: call("slam_head_rope_partial", _p(src2d), _ld(src2d), col0, _p(cos), _p(sin), 1 if inverse else 0, B, T, H, D,
+                        int(rot_dim), _p(positions), _s()),
+           nbytes=4.0 * M * H * int(rot_dim))
 
 
 def _norm_w(w, H, D, name):
@@ -649,12 +668,13 @@ def attn_bwd(q2d, k2d, v2d, o2d, do2d, lse, dq2d, dk2d, dv2d, B, T, Hq, Hkv, D, 
 
 
 def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, prompt_start, k_gen, v_gen, ancestors,
-                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None, qk_norm=None, prompt_end=None):
+                gen_count_dev, gen_count, beams, Hq, Hkv, D, scale, out, qkv_bias=None, qk_norm=None, prompt_end=None, rot_dim=None):
     """one decode step of attention per hypothesis: (q|k|v bias +) LoRA delta + RoPE + KV append of the new token, then one
     query per row against [prompt KV of its batch item | generated KV via the ancestor table].  qkv_bias: fp32
     [(Hq + 2 Hkv) D] (Qwen2) or None.  qk_norm: (q_weight, k_weight, eps), fp32 [D] each (Qwen3: per-head RMSNorm of the new q / k
     behind bias and LoRA delta, before RoPE) or None.  prompt_end: int32 [B] or None; given, the prompt keys of item b are the slots
-    [prompt_start[b], prompt_end[b]) of its block (right-padded batches) and the call goes through slam_attn_decode_span."""
+    [prompt_start[b], prompt_end[b]) of its block (right-padded batches) and the call goes through slam_attn_decode_span.
+    rot_dim < D (partial rotary, Phi-3 / Phi-4): slam_attn_decode_partial; the tables then hold cos = 1, sin = 0 behind column rot_dim/2."""
     R, G = k_gen.shape[0], k_gen.shape[1]
     Tp = k_prompt.shape[1]
     args = (_p(qkv), _ld(qkv), _p(lora_b), _ld(lora_b) if lora_b is not None else 0, lora_r, _p(cos), _p(sin), _p(positions),
@@ -667,6 +687,11 @@ def attn_decode(qkv, lora_b, lora_r, cos, sin, positions, k_prompt, v_prompt, pr
         _norm_w(qk_norm[1], Hkv, D, "attn_decode")
     if prompt_end is not None:
         assert prompt_end.dtype == torch.int32 and prompt_start is not None and prompt_end.shape == prompt_start.shape
+    if rot_dim is not None and rot_dim != D:
+        qn = qk_norm if qk_norm is not None else (None, None, 0.0)
+        fn = lambda: call("slam_attn_decode_partial", *args, _p(qkv_bias), _p(qn[0]), _p(qn[1]), float(qn[2]), _p(prompt_end),  # noqa: E731
+                          int(rot_dim), _s())
+    elif prompt_end is not None:
         qn = qk_norm if qk_norm is not None else (None, None, 0.0)
         fn = lambda: call("slam_attn_decode_span", *args, _p(qkv_bias), _p(qn[0]), _p(qn[1]), float(qn[2]), _p(prompt_end), _s())  # noqa: E731
     elif qk_norm is not None:

@@ -92,18 +92,21 @@ WAVLM_PRESETS["wavlm-base-plus"] = WAVLM_PRESETS["wavlm-base"]
 
 
 # ---------------------------------------------------------------------------------------------- Hugging Face LLM directories
-HF_LLM_TYPES = ("llama", "qwen2", "qwen3")
+HF_LLM_TYPES = ("llama", "qwen2", "qwen3", "phi3")
 
 
 def hf_rope_scaling(hf_cfg: dict):
     """the rope_scaling dict (make_config key `rope_scaling`) an HF config.json asks for, or None for plain RoPE.  Older configs carry
-    `rope_scaling`, newer ones `rope_parameters` (which also holds rope_theta); llama3 (Llama-3.1 / 3.2) and linear are implemented."""
-    from slam_llm_amd.host_tables import ROPE_SCALING_TYPES, rope_scaling_type
+    `rope_scaling`, newer ones `rope_parameters` (which also holds rope_theta); llama3 (Llama-3.1 / 3.2) and linear are implemented, and
+    longrope for model_type phi3 alone (hf_longrope)."""
+    from slam_llm_amd.host_tables import LONGROPE, ROPE_SCALING_TYPES, rope_scaling_type
     for key in ("rope_scaling", "rope_parameters"):
         sc = hf_cfg.get(key) or {}
         kind = rope_scaling_type(sc)
         if kind == "default":
             continue
+        if kind == LONGROPE and hf_cfg.get("model_type") == "phi3":
+            return hf_longrope(hf_cfg, sc, key)
         if kind not in ROPE_SCALING_TYPES:
             raise NotImplementedError(f"llm_path config.json: scaled RoPE of type {kind!r} is not implemented (the HIP LLM covers "
                                       f"{[t for t in ROPE_SCALING_TYPES if t != 'default']})")
@@ -115,8 +118,57 @@ def hf_rope_scaling(hf_cfg: dict):
     return None
 
 
+def hf_partial_rotary_factor(hf_cfg: dict) -> float:
+    """partial_rotary_factor of a config.json: at the top level (Phi-4-mini's spelling) or inside rope_parameters / rope_scaling"""
+    for src in (hf_cfg, hf_cfg.get("rope_parameters") or {}, hf_cfg.get("rope_scaling") or {}):
+        if src.get("partial_rotary_factor") is not None:
+            return float(src["partial_rotary_factor"])
+    return 1.0
+
+
+def hf_longrope(hf_cfg: dict, sc: dict, key: str) -> dict:
+    """the longrope dict of a Phi3 config.json as host_tables reads it: both factor lists (rotary dims / 2 values each), the pretrained
+    length, and what the attention factor derives from (HF _compute_longrope_parameters)"""
+    d, Hq = int(hf_cfg["hidden_size"]), int(hf_cfg["num_attention_heads"])
+    rot = int(int(hf_cfg.get("head_dim") or d // Hq) * hf_partial_rotary_factor(hf_cfg))
+    orig = sc.get("original_max_position_embeddings") or hf_cfg.get("original_max_position_embeddings")
+    missing = [k for k in ("short_factor", "long_factor") if sc.get(k) is None] + ([] if orig else ["original_max_position_embeddings"])
+    if sc.get("factor") is None and hf_cfg.get("max_position_embeddings") is None:
+        missing.append("factor / max_position_embeddings")
+    if missing:
+        raise ValueError(f"llm_path config.json: {key} of type 'longrope' lacks {missing}")
+    for k in ("short_factor", "long_factor"):
+        if len(sc[k]) != rot // 2:
+            raise ValueError(f"llm_path config.json: longrope {k} holds {len(sc[k])} values, the rotary dims ask for {rot // 2}")
+    out = dict(rope_type="longrope", short_factor=[float(x) for x in sc["short_factor"]], long_factor=[float(x) for x in sc["long_factor"]],
+               original_max_position_embeddings=int(orig))
+    if sc.get("factor") is not None:
+        out["factor"] = float(sc["factor"])
+    else:
+        out["max_position_embeddings"] = int(hf_cfg["max_position_embeddings"])
+    if sc.get("attention_factor") is not None:
+        out["attention_factor"] = float(sc["attention_factor"])
+    return out
+
+
+def hf_phi3_geometry(hf_cfg: dict, D: int) -> dict:
+    """what a Phi3ForCausalLM config.json adds: fused qkv_proj / gate_up_proj (llm_fused_proj), partial rotary (llm_rotary_dim), a sliding
+    window that must cover every sequence (llm_sliding_window), the pretrained length generate() must stay under with longrope"""
+    if D not in (64, 128):
+        raise NotImplementedError(f"llm_path config.json: phi3 with head_dim {D} is not implemented (the HIP attention covers 64 and 128)")
+    rot = int(D * hf_partial_rotary_factor(hf_cfg))
+    if rot % 16 != 0 or not 16 <= rot <= D:
+        raise NotImplementedError(f"llm_path config.json: phi3 rotary dims {rot} (head_dim {D} x partial_rotary_factor) must be a multiple "
+                                  f"of 16 in [16, {D}]")
+    for k in ("resid_pdrop", "embd_pdrop", "attention_dropout"):
+        if float(hf_cfg.get(k) or 0.0) != 0.0:
+            raise NotImplementedError(f"llm_path config.json: phi3 with {k}={hf_cfg[k]} is not implemented (the frozen LLM runs without dropout)")
+    win = hf_cfg.get("sliding_window")
+    return dict(llm_fused_proj=True, llm_rotary_dim=rot, llm_sliding_window=int(win) if win else None)
+
+
 def hf_llm_geometry(hf_cfg: dict) -> dict:
-    """make_config keys of the decoder an HF `config.json` (LlamaForCausalLM / Qwen2ForCausalLM / Qwen3ForCausalLM) describes"""
+    """make_config keys of the decoder an HF `config.json` (LlamaForCausalLM / Qwen2ForCausalLM / Qwen3ForCausalLM / Phi3ForCausalLM) describes"""
     mt = hf_cfg.get("model_type")
     if mt not in HF_LLM_TYPES:
         raise NotImplementedError(f"llm_path config.json: model_type {mt!r} is not implemented (the HIP LLM covers {list(HF_LLM_TYPES)})")
@@ -132,11 +184,16 @@ def hf_llm_geometry(hf_cfg: dict) -> dict:
     d, Hq = int(hf_cfg["hidden_size"]), int(hf_cfg["num_attention_heads"])
     # Qwen2 always carries the q/k/v bias; Qwen3 has none unless attention_bias says so, and norms every q / k head (q_norm, k_norm)
     bias = mt == "qwen2" or (mt == "qwen3" and bool(hf_cfg.get("attention_bias", False)))
-    return dict(llm_dim=d, llm_layers=int(hf_cfg["num_hidden_layers"]), llm_heads=Hq,
-                llm_kv_heads=int(hf_cfg.get("num_key_value_heads") or Hq), llm_head_dim=int(hf_cfg.get("head_dim") or d // Hq),
+    D = int(hf_cfg.get("head_dim") or d // Hq)
+    geom = dict(llm_dim=d, llm_layers=int(hf_cfg["num_hidden_layers"]), llm_heads=Hq,
+                llm_kv_heads=int(hf_cfg.get("num_key_value_heads") or Hq), llm_head_dim=D,
                 llm_ffn=int(hf_cfg["intermediate_size"]), vocab=int(hf_cfg["vocab_size"]), rope_theta=float(theta),
                 rms_eps=float(hf_cfg.get("rms_norm_eps", 1e-6)), llm_qkv_bias=bias, llm_qk_norm=mt == "qwen3",
-                rope_scaling=hf_rope_scaling(hf_cfg), tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)))
+                rope_scaling=None, tie_embeddings=bool(hf_cfg.get("tie_word_embeddings", False)))
+    if mt == "phi3":    # before the RoPE rule: its factor lists are checked against the rotary dims
+        geom.update(hf_phi3_geometry(hf_cfg, D))
+    geom["rope_scaling"] = hf_rope_scaling(hf_cfg)
+    return geom
 
 
 def read_hf_llm_config(llm_path):
