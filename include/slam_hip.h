@@ -177,6 +177,12 @@ int slam_attn_set_bwd_variant(int variant);   /* tools: 0 = DMA-ring backward ke
  * tensors beyond 2 GiB, the tools' variants), NULL otherwise.  flags: bit 0 = dropout, bit 1 = relative position bias. */
 int slam_attn_needs_transposed(int64_t B, int64_t Tq, int64_t Tk, int64_t Hq, int64_t Hkv, int64_t D, int64_t ldq, int64_t ldk,
                                int64_t ldv, int64_t lddo, int flags);
+/* The kernels a call runs under the current knobs, by name with their template arguments, e.g.
+ * "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,true>"; backward: "dQ kernel + dK/dV kernel".  Answered by attn_plan(), the
+ * function slam_attn_fwd / slam_attn_bwd / slam_attn_needs_transposed dispatch on; host code only, no device is touched.  present: bits 0 / 1 as
+ * the flags above, 2 = V row-major, 3 = the Vt copy, 4 = key mask, 5 = packed segments, 6 = LSE output, 7 = pre-scaled Q (negative scale). */
+int slam_attn_kernel_name(int backward, int64_t B, int64_t Tq, int64_t Tk, int64_t Tqp, int64_t Tkp, int64_t Hq, int64_t Hkv, int64_t D,
+                          int64_t ldq, int64_t ldk, int64_t ldv, int64_t lddo, int causal, int present, char* out, int64_t out_bytes);
 int slam_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, const void* V, int64_t ldv, void* O,
                   int64_t ldo, float* LSE, const uint8_t* key_mask, int64_t B, int64_t Tq, int64_t Tk,
                   int64_t Tqp, int64_t Tkp, int64_t Hq, int64_t Hkv, int64_t D, int causal, float scale,

@@ -26,6 +26,7 @@
 // never masked.  A row with no visible key yields O = 0, LSE = +inf (P = 0 in the backward)
 // so pad rows stay finite.  Positions/rows beyond T are handled by clamped/zero loads and guarded stores.
 #include "attn_common.h"
+#include <utility>
 
 namespace {
 
@@ -2209,94 +2210,191 @@ __global__ __launch_bounds__(256) void relpos_dtab_kernel(const float* __restric
   dtab[(int64_t)h * rp_ld + r] += acc;
 }
 
-int g_attn_tr = 1;    // 1 = transposed operands by ds_read_b64_tr_b16 from the row-major tiles (shipped), 0 = round-3 kernels on the [B,H,D,Tp] copies
-int g_attn_xcd = 1;   // 1 = XCD-aware workgroup numbering (shipped), 0 = hardware round-robin order (A/B in tools)
-int g_attn_heavy = 1; // 1 = causal launches start each XCD's heaviest sequence blocks first (round 5), 0 = id order (A/B: slam_attn_set_fwd_qf 50 / 51)
+// ---- host side: the knobs, attn_plan() -- the one place that decides which kernels a call runs -- and the entry points that ask it ----
+struct AttnKnobs {       // the defaults live here and only here (slam_reset_tuning assigns a default-constructed value)
+  int tr = 1;            // 1 = transposed operands by ds_read_b64_tr_b16 from the row-major tiles (shipped), 0 = round-3 kernels on the [B,H,D,Tp] copies
+  int xcd = 1;           // 1 = XCD-aware workgroup numbering (shipped), 0 = hardware round-robin order (A/B in tools)
+  int heavy = 1;         // 1 = causal launches start each XCD's heaviest sequence blocks first (round 5), 0 = id order (A/B: slam_attn_set_fwd_qf 50 / 51)
+  int bwd_variant = 0;   // 0 = ring kernels (shipped), 1 = round-1 kernels, 2 = ring dK/dV + register-staged dQ (A/B in tools); 14 = cycle stamps, 11 12 15 19 = timing ablations
+  int fwd_qf = 0;        // 16-row query fragments per wave of the forward kernel: 0 = auto, 1 / 2 forced (tools)
+  int fwd_qs = 1;        // 1 = LSE-less launches of the mask-free form whose Q arrives pre-scaled (negative scale) run attn_fwd_kernel<..., QS>
+  int fwd_plain = 1;     // 1 = unmasked bidirectional D = 64 launches (Whisper) take the instantiation without mask / segment bookkeeping
+  int fwd_dma = 1;       // 1 = K / V^T tiles by LDS-DMA ring (shipped), 0 = register-staged tiles (A/B in tools)
+};
+AttnKnobs g_attn;
 
 // every attention kernel is launched through this: logical 3-D grid -> 1-D launch + the geometry attn_blk() needs
 template <class Kern>
-static void attn_launch(Kern kern, dim3 grid, unsigned threads, int lds, hipStream_t s, AttnParams p, int heavy = 0) {
+void attn_launch(Kern kern, dim3 grid, unsigned threads, int lds, hipStream_t s, AttnParams p, int heavy) {
   p.gx = (int)grid.x; p.gy = (int)grid.y; p.gz = (int)grid.z;
-  p.xcd = g_attn_xcd;
-  p.heavy = (g_attn_heavy && !p.seg_lo) ? heavy : 0;   // (packed batches: a block's work follows its segment, not its index)
+  p.xcd = g_attn.xcd;
+  p.heavy = (g_attn.heavy && !p.seg_lo) ? heavy : 0;   // (packed batches: a block's work follows its segment, not its index)
   hipLaunchKernelGGL(kern, dim3(grid.x * grid.y * grid.z), dim3(threads), lds, s, p);
 }
 
-template <int D, bool CAUSAL, int QF, bool PROBE = false>
-int launch_dq_ring(const AttnParams& p, dim3 grid, hipStream_t s) {
-  constexpr int lds = 3 * (3 * 32 * D * 2 + 1024);
+// the ring and transposed-read kernels want more dynamic LDS than the default limit: raised once per kernel, then attn_launch
+template <auto Kern>
+int attn_launch_lds(dim3 grid, unsigned threads, int lds, hipStream_t s, const AttnParams& p, int heavy) {
   static bool attr_set = false;
-  auto kern = attn_bwd_dq_ring_kernel<D, CAUSAL, QF, PROBE>;
-  constexpr int heavy = CAUSAL ? -1 : 0;
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
       slam_set_error("slam_attn_bwd: cannot raise the LDS limit to %d", lds);
       return -2;
     }
     attr_set = true;
   }
-  attn_launch(kern, grid, 256, lds, s, p, heavy);
+  attn_launch(Kern, grid, threads, lds, s, p, heavy);
+  return 0;
+}
+
+// what attn_plan() is asked: one call of slam_attn_fwd / slam_attn_bwd, by shape and by which optional operands are present
+struct AttnCall {
+  bool bwd;
+  int64_t B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, ldq, ldk, ldv, lddo;
+  bool causal, v, vt, kmask, seg, lse, qpre, rp, drop;   // row-major V, its [B,H,D,Tp] copy, key mask, packed segments, LSE output, pre-scaled Q, relative position bias, dropout
+};
+
+// what the 32-bit byte offsets of the DMA descriptors can address: the row-major operands (Q / dO and K / V live inside fused buffers:
+// ld = 3 H D for a QKV buffer, so the range is exhausted ~3x sooner than H D would suggest), and the [B,H,D,Tp] copies of the round-3
+// ring kernels.  ONE predicate for every launch, forward and backward (they used to differ, and the dK / dV launch did not
+// look at all -- beyond 2 GiB its descriptor reads would have returned zeros, silently).
+struct AttnFits { bool k, v, kvcopy, rowmajor, copies; };   // K, V row-major; the K-side copy; all four row-major operands; both copies
+AttnFits attn_fits(const AttnCall& c) {
+  const int64_t lim = (int64_t)1 << 31;
+  AttnFits f;
+  f.k = (c.B * c.Tk * c.ldk + c.Hkv * c.D) * 2 < lim;
+  f.v = (c.B * c.Tk * c.ldv + c.Hkv * c.D) * 2 < lim;
+  f.kvcopy = c.B * c.Hkv * c.D * c.Tkp * 2 < lim;
+  f.rowmajor = f.k && f.v && (c.B * c.Tq * c.ldq + c.Hq * c.D) * 2 < lim && (c.B * c.Tq * c.lddo + c.Hq * c.D) * 2 < lim;
+  f.copies = f.kvcopy && c.B * c.Hq * c.D * c.Tqp * 2 < lim;
+  return f;
+}
+
+enum AttnForm { STAGED, RING, TR };   // register-staged tiles (reads the copies) | DMA ring on the copies (round 3) | DMA ring + transposing LDS reads (shipped)
+struct AttnPlan {
+  bool ok;                   // false: a timing-ablation variant whose tensors the descriptors cannot address
+  int qf;                    // query fragments per wave: of attn_fwd_kernel, or of the dQ kernel
+  bool rp, drop, probe;      // relative position bias, dropout, cycle stamps (variant 14): forward kernel, or dQ (+ dK / dV for rp, drop)
+  bool dma, plain, trv, qs;  // forward: the remaining template arguments of attn_fwd_kernel
+  AttnForm dq, dkdv;         // backward
+  bool ablation; int abl;    // backward, variants above 10 at D = 128 causal: attn_bwd_dkdv_ring_kernel<128, true, abl>
+  int heavy;                 // sign handed to attn_launch by the forward and dQ launches; dK / dV takes the opposite one
+  dim3 gq, gk;               // logical grids: forward and dQ | dK / dV
+  bool reads_copies;         // a planned kernel reads a [B,H,D,Tp] copy (forward: Vt; backward: Qt / Kt / dOt)
+};
+
+// THE dispatch rule: pure in the call and the knobs.  slam_attn_fwd / slam_attn_bwd launch what it says, slam_attn_needs_transposed and
+// slam_attn_kernel_name report it.  (profiles/attn_plan.md lists the corners it keeps as they were found.)
+AttnPlan attn_plan(const AttnCall& c) {
+  const AttnKnobs& g = g_attn;
+  const AttnFits f = attn_fits(c);
+  const bool special = c.rp || c.drop;   // WavLM's bias / attention dropout: <64, false, ...> forms only, on register-staged backward kernels
+  AttnPlan pl = {};
+  pl.rp = c.rp; pl.drop = c.drop;
+  pl.heavy = c.causal ? -1 : 0;
+  if (!c.bwd) {
+    pl.ok = true;
+    pl.probe = !special && g.bwd_variant == 14 && c.D == 64 && !c.causal;   // tools/attn_fwd_probe.py: no TRV / PLAIN form, reads Vt
+    // measured (tools/attn_bwd_bench.py, interleaved): with LDS-DMA tiles two fragments per wave win at both head sizes (D = 128,
+    // Llama shape: 86 vs 108 us -- half the DMA pieces per query, and no staging registers push it past 256 VGPRs any more); with
+    // register-staged tiles (tensors beyond the descriptors' 2 GiB) D = 128 prefers one fragment (119 vs 134 us: 261 VGPRs = one
+    // wave per SIMD with two).  (This test looks at the K-side COPY, the DMA test below at what the launch reads.)
+    pl.qf = (special || pl.probe) ? 2 : g.fwd_qf ? g.fwd_qf : (c.D == 128 && !(g.fwd_dma && f.k && f.kvcopy)) ? 1 : 2;
+    // row-major V whenever the caller passed it (and the [B,H,D,Tp] copy only when it did not, or for the A/B knob)
+    const bool trv = c.v && (g.tr || !c.vt);
+    pl.dma = g.fwd_dma && f.k && (trv ? f.v : f.kvcopy);
+    pl.trv = trv && !pl.probe;
+    pl.plain = pl.dma && c.D == 64 && !c.causal && pl.qf == 2 && !special && !pl.probe && !c.kmask && !c.seg && g.fwd_plain;
+    // Q pre-scaled by the caller and no LSE wanted (the frozen encoder's forward): accumulators start at -m
+    pl.qs = pl.plain && pl.trv && !c.lse && c.qpre && g.fwd_qs;
+    pl.reads_copies = !pl.trv;
+  } else {
+    // dQ: 32 queries per wave (128 per workgroup) once there is more than one 64-query block; dQ and dK / dV: the descriptor (DMA
+    // ring) forms whenever attn_fits says their descriptors reach -- transposing reads, or with knob 40 the round-3 kernels on the copies
+    const bool ring_ok = f.rowmajor && f.copies, wide = !special && c.Tq > 64 && g.bwd_variant != 1;
+    const AttnForm desc = g.tr ? (f.rowmajor ? TR : STAGED) : (ring_ok ? RING : STAGED);
+    pl.ablation = !special && g.bwd_variant > 10 && c.D == 128 && c.causal;   // timing ablations of the D = 128 causal ring kernel (tools only)
+    pl.ok = !pl.ablation || ring_ok;
+    pl.abl = g.bwd_variant == 11 ? 1 : g.bwd_variant == 12 ? 2 : g.bwd_variant == 19 ? 9 : g.bwd_variant == 14 ? 0 : 5;
+    pl.qf = wide ? 2 : 1;
+    pl.probe = wide && pl.ablation && g.bwd_variant == 14 && ring_ok;
+    pl.dq = pl.probe ? RING : (!wide || g.bwd_variant == 2) ? STAGED : desc;
+    pl.dkdv = pl.ablation ? RING : (special || g.bwd_variant == 1) ? STAGED : desc;   // (no <= 64-query test: the ring dK / dV kernels take any Tq)
+    pl.gk = dim3((unsigned)cdiv64(c.Tk, pl.dkdv == STAGED ? 64 : 128), (unsigned)c.Hkv, (unsigned)c.B);
+    pl.reads_copies = pl.dq != TR || pl.dkdv != TR;
+  }
+  pl.gq = dim3((unsigned)cdiv64(c.Tq, 64 * pl.qf), (unsigned)c.Hq, (unsigned)c.B);
+  return pl;
+}
+
+// the planned kernels by name, template arguments as the kernels declare them (backward: dQ + dK / dV)
+int attn_label(const AttnCall& c, const AttnPlan& pl, char* out, size_t n) {
+  const char* const tf[2] = {"false", "true"};
+  const int D = (int)c.D;
+  const char* C = tf[c.causal];
+  if (!c.bwd)
+    return snprintf(out, n, "attn_fwd_kernel<%d,%s,%d,%s,%s,%s,%s,%s,%s,%s>", D, C, pl.qf, tf[pl.rp], tf[pl.drop], tf[pl.probe], tf[pl.dma],
+                    tf[pl.plain], tf[pl.trv], tf[pl.qs]);
+  char dq[64], dkdv[64];
+  if (pl.dq == STAGED) snprintf(dq, sizeof dq, "attn_bwd_dq_kernel<%d,%s,%s,%d,%s>", D, C, tf[pl.drop], pl.qf, tf[pl.rp]);
+  else if (pl.dq == RING) snprintf(dq, sizeof dq, "attn_bwd_dq_ring_kernel<%d,%s,%d,%s>", D, C, pl.qf, tf[pl.probe]);
+  else snprintf(dq, sizeof dq, "attn_bwd_dq_tr_kernel<%d,%s,%d>", D, C, pl.qf);
+  if (pl.dkdv == STAGED) snprintf(dkdv, sizeof dkdv, "attn_bwd_dkdv_kernel<%d,%s,%s,%s>", D, C, tf[pl.drop], tf[pl.rp]);
+  else if (pl.dkdv == RING) snprintf(dkdv, sizeof dkdv, "attn_bwd_dkdv_ring_kernel<%d,%s,%d>", D, C, pl.ablation ? pl.abl : 0);
+  else snprintf(dkdv, sizeof dkdv, "attn_bwd_dkdv_tr_kernel<%d,%s>", D, C);
+  return snprintf(out, n, "%s + %s", dq, dkdv);
+}
+
+// ---- forward launch.  The instantiations of attn_fwd_kernel that exist: RP / DROP / PROBE only as <64, false, 2>, PROBE without TRV,
+// PLAIN only as the DMA form of <64, false, 2> without RP / DROP / PROBE, QS only on PLAIN + TRV.  A key packs the ten template
+// arguments; fwd_launch tries the keys from the largest down (the order the object file lists the kernels in) and launches the match.
+constexpr int fwd_key(int D, bool C, int QF, bool RP, bool DROP, bool PROBE, bool DMA, bool PLAIN, bool TRV, bool QS) {
+  return DROP << 9 | RP << 8 | PROBE << 7 | (D == 64) << 6 | C << 5 | (QF == 2) << 4 | TRV << 3 | QS << 2 | PLAIN << 1 | (int)DMA;
+}
+template <int K>
+bool fwd_try(int key, dim3 grid, hipStream_t s, const AttnParams& p, int heavy) {
+  constexpr int D = (K >> 6 & 1) ? 64 : 128, QF = (K >> 4 & 1) ? 2 : 1;
+  constexpr bool DROP = K >> 9 & 1, RP = K >> 8 & 1, PROBE = K >> 7 & 1, C = K >> 5 & 1, TRV = K >> 3 & 1, QS = K >> 2 & 1, PLAIN = K >> 1 & 1, DMA = K & 1;
+  constexpr bool base = D == 64 && !C && QF == 2, special = RP || DROP || PROBE;
+  if constexpr ((!special || base) && !(PROBE && (RP || DROP || TRV)) && (!PLAIN || (base && !special && DMA)) && (!QS || (PLAIN && TRV))) {
+    if (key == K) {
+      attn_launch(attn_fwd_kernel<D, C, QF, RP, DROP, PROBE, DMA, PLAIN, TRV, QS>, grid, 256, 0, s, p, heavy);
+      return true;
+    }
+  }
+  return false;
+}
+template <int... I>
+bool fwd_launch(std::integer_sequence<int, I...>, int key, dim3 grid, hipStream_t s, const AttnParams& p, int heavy) {
+  return (... || fwd_try<1023 - I>(key, grid, s, p, heavy));
+}
+
+// ---- backward launches: dQ and dK / dV of one <D, CAUSAL>
+template <int D, bool CAUSAL>
+int launch_dq(const AttnPlan& pl, const AttnParams& p, hipStream_t s) {
+  if constexpr (D == 128 && CAUSAL) {
+    if (pl.probe) return attn_launch_lds<attn_bwd_dq_ring_kernel<D, CAUSAL, 2, true>>(pl.gq, 256, 3 * (3 * 32 * D * 2 + 1024), s, p, pl.heavy);
+  }
+  if (pl.dq == TR) return attn_launch_lds<attn_bwd_dq_tr_kernel<D, CAUSAL, 2>>(pl.gq, 256, 3 * (2 * 32 * D * 2 + 1024), s, p, pl.heavy);
+  if (pl.dq == RING) return attn_launch_lds<attn_bwd_dq_ring_kernel<D, CAUSAL, 2>>(pl.gq, 256, 3 * (3 * 32 * D * 2 + 1024), s, p, pl.heavy);
+  if (pl.qf == 2) attn_launch(attn_bwd_dq_kernel<D, CAUSAL, false, 2>, pl.gq, 256, 0, s, p, pl.heavy);   // (reads Kt: the plan says reads_copies)
+  else attn_launch(attn_bwd_dq_kernel<D, CAUSAL, false, 1>, pl.gq, 256, 0, s, p, pl.heavy);
   return 0;
 }
 
 template <int D, bool CAUSAL, int ABL = 0>
-int launch_dkdv_ring(const AttnParams& p, dim3 grid, hipStream_t s) {
-  constexpr int lds = 4 * (4 * 32 * D * 2 + 1024);
-  static bool attr_set = false;
-  auto kern = attn_bwd_dkdv_ring_kernel<D, CAUSAL, ABL>;
-  constexpr int heavy = CAUSAL ? 1 : 0;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      slam_set_error("slam_attn_bwd: cannot raise the LDS limit to %d", lds);
-      return -2;
-    }
-    attr_set = true;
-  }
-  attn_launch(kern, grid, 512, lds, s, p, heavy);
-  return 0;
+int launch_dkdv_ring(const AttnPlan& pl, const AttnParams& p, hipStream_t s) {
+  return attn_launch_lds<attn_bwd_dkdv_ring_kernel<D, CAUSAL, ABL>>(pl.gk, 512, 4 * (4 * 32 * D * 2 + 1024), s, p, -pl.heavy);
 }
-
-template <int D, bool CAUSAL, int QF>
-int launch_dq_tr(const AttnParams& p, dim3 grid, hipStream_t s) {
-  constexpr int lds = 3 * (2 * 32 * D * 2 + 1024);
-  static bool attr_set = false;
-  auto kern = attn_bwd_dq_tr_kernel<D, CAUSAL, QF>;
-  constexpr int heavy = CAUSAL ? -1 : 0;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      slam_set_error("slam_attn_bwd: cannot raise the LDS limit to %d", lds);
-      return -2;
-    }
-    attr_set = true;
-  }
-  attn_launch(kern, grid, 256, lds, s, p, heavy);
-  return 0;
-}
-
-}  // namespace
-// (round 5's 4-wave x 32-key form of the kernel below -- half the LDS bytes per MFMA, bit-identical, 11 % slower, profiles/r05_attention_dkdv32.md --
-// was removed in round 6 with its translation unit; git history keeps it)
-namespace {
 
 template <int D, bool CAUSAL>
-int launch_dkdv_tr(const AttnParams& p, dim3 grid, hipStream_t s) {
-  constexpr int lds = 4 * (2 * 32 * D * 2 + 1024);
-  static bool attr_set = false;
-  auto kern = attn_bwd_dkdv_tr_kernel<D, CAUSAL>;
-  constexpr int heavy = CAUSAL ? 1 : 0;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      slam_set_error("slam_attn_bwd: cannot raise the LDS limit to %d", lds);
-      return -2;
-    }
-    attr_set = true;
-  }
-  attn_launch(kern, grid, 512, lds, s, p, heavy);
+int launch_bwd(const AttnPlan& pl, const AttnParams& p, hipStream_t s) {
+  if (int rc = launch_dq<D, CAUSAL>(pl, p, s)) return rc;
+  if (pl.dkdv == TR) return attn_launch_lds<attn_bwd_dkdv_tr_kernel<D, CAUSAL>>(pl.gk, 512, 4 * (2 * 32 * D * 2 + 1024), s, p, -pl.heavy);
+  if (pl.dkdv == RING) return launch_dkdv_ring<D, CAUSAL>(pl, p, s);
+  attn_launch(attn_bwd_dkdv_kernel<D, CAUSAL>, pl.gk, 256, 0, s, p, -pl.heavy);
   return 0;
 }
-
-int g_attn_bwd_variant = 0;   // 0 = ring kernels (shipped), 1 = round-1 kernels, 2 = ring dK/dV + register-staged dQ (A/B in tools)
-int g_attn_fwd_qf = 0;   // 16-row query fragments per wave of the forward kernel: 0 = auto, 1 / 2 forced (tools)
 
 int check_common(const char* name, int64_t B, int64_t Tq, int64_t Tk, int64_t Tqp, int64_t Tkp, int64_t Hq, int64_t Hkv,
                  int64_t D, int causal) {
@@ -2323,97 +2421,58 @@ extern "C" int slam_attn_debug_clock(unsigned long long* out256) {   // tools: s
 
 extern "C" int slam_attn_set_bwd_variant(int variant) {   // tools: 0 = DMA-ring backward kernels (shipped), 1 = round-1 kernels
   SLAM_CHECK_ARG(variant == 0 || variant == 1 || variant == 2 || variant == 14 || variant == 11 || variant == 12 || variant == 15 || variant == 19, "slam_attn_set_bwd_variant: %d (0 | 1 | 2 | 11, 12, 15 timing ablations)", variant);
-  g_attn_bwd_variant = variant;
+  g_attn.bwd_variant = variant;
   return 0;
 }
 
-extern int g_attn_fwd_dma, g_attn_fwd_plain, g_attn_fwd_qs;
 extern "C" int slam_attn_set_fwd_qf(int qf) {   // tools: 0 = auto, 1 / 2 fragments per wave; 10 / 11 = register-staged / DMA tiles
   SLAM_CHECK_ARG((qf >= 0 && qf <= 2) || qf == 10 || qf == 11 || qf == 20 || qf == 21 || qf == 30 || qf == 31 || qf == 40 || qf == 41 || qf == 50 || qf == 51 || qf == 60 || qf == 61,
                  "slam_attn_set_fwd_qf: %d (0 = auto, 1 or 2; 10 / 11 = staged / DMA tiles; 20 / 21 = hardware / XCD-aware workgroup order; "
                  "30 / 31 = general / mask-free instantiation for unmasked bidirectional D = 64; 40 / 41 = transposed-copy / transposed-read kernels; "
                  "50 / 51 = id order / heaviest sequence block first in causal launches; 60 / 61 = general softmax / Q pre-scaled by the caller "
                  "and accumulators started at -m in LSE-less mask-free launches)", qf);
-  if (qf >= 60) g_attn_fwd_qs = qf - 60;
-  else if (qf >= 50) g_attn_heavy = qf - 50;
-  else if (qf >= 40) g_attn_tr = qf - 40;
-  else if (qf >= 30) g_attn_fwd_plain = qf - 30;
-  else if (qf >= 20) g_attn_xcd = qf - 20;   // (all attention kernels, forward and backward)
-  else if (qf >= 10) g_attn_fwd_dma = qf - 10;
-  else g_attn_fwd_qf = qf;
+  if (qf >= 60) g_attn.fwd_qs = qf - 60;
+  else if (qf >= 50) g_attn.heavy = qf - 50;
+  else if (qf >= 40) g_attn.tr = qf - 40;
+  else if (qf >= 30) g_attn.fwd_plain = qf - 30;
+  else if (qf >= 20) g_attn.xcd = qf - 20;   // (all attention kernels, forward and backward)
+  else if (qf >= 10) g_attn.fwd_dma = qf - 10;
+  else g_attn.fwd_qf = qf;
   return 0;
 }
 
-// every attention tuning knob back to the value it is DEFINED with (slam_reset_tuning)
-void slam_attn_reset_tuning_() {
-  g_attn_tr = 1; g_attn_xcd = 1; g_attn_heavy = 1; g_attn_bwd_variant = 0; g_attn_fwd_qf = 0;
-  g_attn_fwd_qs = 1; g_attn_fwd_plain = 1; g_attn_fwd_dma = 1;
-}
+void slam_attn_reset_tuning_() { g_attn = AttnKnobs(); }   // (slam_reset_tuning)
 
-int g_attn_fwd_qs = 1;    // 1 = LSE-less launches of the mask-free form whose Q arrives pre-scaled (negative scale) run attn_fwd_kernel<..., QS>
-int g_attn_fwd_plain = 1; // 1 = unmasked bidirectional D = 64 launches (Whisper) take the instantiation without mask / segment bookkeeping
-int g_attn_fwd_dma = 1;   // 1 = K / V^T tiles by LDS-DMA ring (shipped), 0 = register-staged tiles (A/B in tools)
-
-// forward launch: the DMA form whenever the 32-bit byte offsets of its descriptors can address K and V^T
-template <int D, bool CAUSAL, int QF, bool RP = false, bool DROP = false, bool PROBE = false>
-static void launch_fwd(const AttnParams& p, int64_t B, hipStream_t s) {
-  dim3 grid((unsigned)cdiv64(p.Tq, 64 * QF), (unsigned)p.Hq, (unsigned)B);
-  const int64_t lim = (int64_t)1 << 31;
-  // row-major V whenever the caller passed it (and the [B,H,D,Tp] copy only when it did not, or for the A/B knob)
-  const bool trv = p.V != nullptr && (g_attn_tr || p.Vt == nullptr);
-  const bool fits = (B * p.Tk * p.ldk + (int64_t)p.Hkv * D) * 2 < lim &&
-                    (trv ? (B * p.Tk * p.ldv + (int64_t)p.Hkv * D) * 2 < lim : B * p.Hkv * D * p.Tkp * 2 < lim);
-  if constexpr (!PROBE) {
-    if (trv) {
-      if constexpr (D == 64 && !CAUSAL && QF == 2 && !RP && !DROP) {
-        if (fits && g_attn_fwd_dma && !p.kmask && !p.seg_lo && g_attn_fwd_plain) {
-          // Q pre-scaled by the caller and no LSE wanted (the frozen encoder's forward): accumulators start at -m
-          if (!p.LSE && p.qpre && g_attn_fwd_qs) attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, true, true, true, true>), grid, 256, 0, s, p, 0);
-          else attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, true, true, true>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-          return;
-        }
-      }
-      if (fits && g_attn_fwd_dma) attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, true, false, true>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-      else attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, false, false, true>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-      return;
-    }
-  }
-  if constexpr (D == 64 && !CAUSAL && QF == 2 && !RP && !DROP && !PROBE) {
-    if (fits && g_attn_fwd_dma && !p.kmask && !p.seg_lo && g_attn_fwd_plain) {
-      attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, true, true>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-      return;
-    }
-  }
-  if (fits && g_attn_fwd_dma) attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, true>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-  else attn_launch((attn_fwd_kernel<D, CAUSAL, QF, RP, DROP, PROBE, false>), grid, 256, 0, s, p, CAUSAL ? -1 : 0);
-}
-
-// what the 32-bit byte offsets of the DMA descriptors can address: the row-major operands (Q / dO and K / V live inside fused buffers:
-// ld = 3 H D for a QKV buffer, so the range is exhausted ~3x sooner than H D would suggest), and the [B,H,D,Tp] copies of the round-3
-// ring kernels.  ONE predicate for slam_attn_needs_transposed and for every backward launch (they used to differ, and the
-// dK / dV launch did not look at all -- beyond 2 GiB its descriptor reads would have returned zeros, silently).
-struct AttnFits { bool rowmajor, copies; };
-static AttnFits attn_fits(int64_t B, int64_t Tq, int64_t Tk, int64_t Tqp, int64_t Tkp, int64_t Hq, int64_t Hkv, int64_t D, int64_t ldq,
-                          int64_t ldk, int64_t ldv, int64_t lddo) {
-  const int64_t lim = (int64_t)1 << 31;
-  AttnFits f;
-  f.rowmajor = (B * Tk * ldk + Hkv * D) * 2 < lim && (B * Tk * ldv + Hkv * D) * 2 < lim &&
-               (B * Tq * ldq + Hq * D) * 2 < lim && (B * Tq * lddo + Hq * D) * 2 < lim;
-  f.copies = B * Hkv * D * Tkp * 2 < lim && B * Hq * D * Tqp * 2 < lim;
-  return f;
-}
-
-// which transposed [B,H,D,Tp] copies a call with these arguments reads (bit 0: slam_attn_fwd needs Vt; bit 1: slam_attn_bwd needs Qt / Kt /
-// dOt).  0 for everything the transposed-read kernels cover; the host side builds the copies (slam_head_rope_transpose) only when asked
-// to.  flags: bit 0 = attention-probability dropout, bit 1 = gated relative position bias (WavLM).
+// which transposed [B,H,D,Tp] copies a call with these arguments reads (bit 0: slam_attn_fwd reads Vt even when the row-major V is
+// given too; bit 1: slam_attn_bwd needs Qt / Kt / dOt): what attn_plan says, for either value of `causal` a call of this shape can have.
+// 0 for everything the transposed-read kernels cover; the host side builds the copies (slam_head_rope_transpose) only when asked to.
+// flags: bit 0 = attention-probability dropout, bit 1 = gated relative position bias (WavLM).
 extern "C" int slam_attn_needs_transposed(int64_t B, int64_t Tq, int64_t Tk, int64_t Hq, int64_t Hkv, int64_t D, int64_t ldq, int64_t ldk,
                                           int64_t ldv, int64_t lddo, int flags) {
   int need = 0;
-  if (!g_attn_tr) return 3;
-  // backward: the transposed-read kernels are the ring forms; <= 64 queries, dropout, the relative position bias, the non-default
-  // variants and tensors beyond the descriptors' 2 GiB stay on the register-staged kernels, which read the copies
-  if (flags != 0 || Tq <= 64 || !attn_fits(B, Tq, Tk, 0, 0, Hq, Hkv, D, ldq, ldk, ldv, lddo).rowmajor || g_attn_bwd_variant != 0) need |= 2;
-  return need;   // (the forward kernel has a transposed-read form of every instantiation, register-staged ones included)
+  for (int causal = 0; causal <= (Tq == Tk ? 1 : 0); causal++)
+    for (int bwd = 0; bwd <= 1; bwd++) {
+      const AttnCall c = {bwd != 0, B, Tq, Tk, 0, 0, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal != 0, true, true, false, false, true, false, (flags & 2) != 0, (flags & 1) != 0};
+      if (attn_plan(c).reads_copies) need |= 1 << bwd;
+    }
+  return need;
+}
+
+// the kernels a call runs, by name (host code only).  present: bit 0 = dropout, bit 1 = relative position bias (the flags of
+// slam_attn_needs_transposed), 2 = row-major V, 3 = the Vt copy, 4 = key mask, 5 = packed segments, 6 = LSE output, 7 = pre-scaled Q
+extern "C" int slam_attn_kernel_name(int backward, int64_t B, int64_t Tq, int64_t Tk, int64_t Tqp, int64_t Tkp, int64_t Hq, int64_t Hkv, int64_t D,
+                                     int64_t ldq, int64_t ldk, int64_t ldv, int64_t lddo, int causal, int present, char* out, int64_t out_bytes) {
+  SLAM_CHECK_ARG(out != nullptr && out_bytes > 0, "slam_attn_kernel_name: no output buffer");
+  if (int rc = check_common("slam_attn_kernel_name", B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, causal)) return rc;
+  SLAM_CHECK_ARG(!(present & 3) || (D == 64 && !causal), "slam_attn_kernel_name: dropout and the relative position bias need head_dim 64, bidirectional");
+  SLAM_CHECK_ARG(backward || (present & 12), "slam_attn_kernel_name: a forward call has V row-major (bit 2) and / or its copy Vt (bit 3)");
+  const AttnCall c = {backward != 0, B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal != 0, (present & 4) != 0, (present & 8) != 0,
+                      (present & 16) != 0, (present & 32) != 0, (present & 64) != 0, (present & 128) != 0, (present & 2) != 0, (present & 1) != 0};
+  const AttnPlan pl = attn_plan(c);
+  SLAM_CHECK_ARG(pl.ok, "slam_attn_kernel_name: the timing-ablation variants need tensors within the descriptors' 2 GiB");
+  const int n = attn_label(c, pl, out, (size_t)out_bytes);
+  SLAM_CHECK_ARG(n >= 0 && n < out_bytes, "slam_attn_kernel_name: the label needs %d bytes, the buffer has %ld", n + 1, (long)out_bytes);
+  return 0;
 }
 
 extern "C" int slam_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* Vt, const void* V, int64_t ldv,
@@ -2450,67 +2509,15 @@ extern "C" int slam_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t 
   p.drop_scale = 1.0f / (1.0f - drop_p);
   p.drop_seed = drop_seed;
   p.drop_salt = g_slam_drop_salt;
-  hipStream_t s = (hipStream_t)stream;
-  if (drop_p > 0.f && rp_gate) {   // un-frozen WavLM in train mode: attention_dropout on top of the gated bias (WavLM.py:181, modules.py:504-562)
-    launch_fwd<64, false, 2, true, true>(p, B, s);
-  } else if (drop_p > 0.f) {
-    launch_fwd<64, false, 2, false, true>(p, B, s);
-  } else if (rp_gate) {
-    launch_fwd<64, false, 2, true>(p, B, s);
-  } else if (g_attn_bwd_variant == 14 && D == 64 && !causal) {   // tools/attn_fwd_probe.py: the same kernel with cycle stamps
-    launch_fwd<64, false, 2, false, false, true>(p, B, s);
-  } else {
-    // measured (tools/attn_bwd_bench.py, interleaved): with LDS-DMA tiles two fragments per wave win at both head sizes (D = 128,
-    // Llama shape: 86 vs 108 us -- half the DMA pieces per query, and no staging registers push it past 256 VGPRs any more); with
-    // register-staged tiles (tensors beyond the descriptors' 2 GiB) D = 128 prefers one fragment (119 vs 134 us: 261 VGPRs = one
-    // wave per SIMD with two)
-    const int64_t lim = (int64_t)1 << 31;
-    const bool dma = g_attn_fwd_dma && (B * Tk * ldk + Hkv * D) * 2 < lim && B * Hkv * D * Tkp * 2 < lim;
-    const int qf = g_attn_fwd_qf ? g_attn_fwd_qf : ((D == 128 && !dma) ? 1 : 2);
-    if (D == 64) {
-      if (causal) { if (qf == 2) launch_fwd<64, true, 2>(p, B, s); else launch_fwd<64, true, 1>(p, B, s); }
-      else { if (qf == 2) launch_fwd<64, false, 2>(p, B, s); else launch_fwd<64, false, 1>(p, B, s); }
-    } else {
-      if (causal) { if (qf == 2) launch_fwd<128, true, 2>(p, B, s); else launch_fwd<128, true, 1>(p, B, s); }
-      else { if (qf == 2) launch_fwd<128, false, 2>(p, B, s); else launch_fwd<128, false, 1>(p, B, s); }
-    }
+  const AttnCall c = {false, B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, ldq, ldk, ldv, 0, causal != 0, V != nullptr, Vt != nullptr, key_mask != nullptr,
+                      seg_lo != nullptr, LSE != nullptr, p.qpre != 0, rp_gate != nullptr, drop_p > 0.f};
+  const AttnPlan pl = attn_plan(c);
+  const int key = fwd_key((int)D, c.causal, pl.qf, pl.rp, pl.drop, pl.probe, pl.dma, pl.plain, pl.trv, pl.qs);
+  if (!fwd_launch(std::make_integer_sequence<int, 1024>(), key, pl.gq, (hipStream_t)stream, p, pl.heavy)) {
+    slam_set_error("slam_attn_fwd: no attn_fwd_kernel instantiation for plan key %d", key);
+    return -2;
   }
   SLAM_CHECK_LAUNCH("slam_attn_fwd");
-  return 0;
-}
-
-// dQ launch: 32 queries per wave (128 per workgroup) once there is more than one 64-query block; the descriptor (DMA ring) forms
-// whenever attn_fits says their descriptors reach (variant 2: register-staged form, for A/B in tools)
-template <int D, bool CAUSAL>
-static int launch_dq(const AttnParams& p, int64_t B, hipStream_t s, AttnFits fits) {
-  if (p.Tq > 64 && g_attn_bwd_variant != 1) {
-    dim3 g2((unsigned)cdiv64(p.Tq, 128), (unsigned)p.Hq, (unsigned)B);
-    if (fits.rowmajor && fits.copies && g_attn_bwd_variant == 14) {
-      if constexpr (D == 128 && CAUSAL) return launch_dq_ring<D, CAUSAL, 2, true>(p, g2, s);
-    }
-    if (g_attn_bwd_variant != 2) {
-      if (g_attn_tr && fits.rowmajor) return launch_dq_tr<D, CAUSAL, 2>(p, g2, s);
-      if (!g_attn_tr && fits.rowmajor && fits.copies) return launch_dq_ring<D, CAUSAL, 2>(p, g2, s);
-    }
-    attn_launch((attn_bwd_dq_kernel<D, CAUSAL, false, 2>), g2, 256, 0, s, p, CAUSAL ? -1 : 0);      // (reads Kt: slam_attn_needs_transposed asked for it)
-  } else {
-    dim3 g1((unsigned)cdiv64(p.Tq, 64), (unsigned)p.Hq, (unsigned)B);
-    attn_launch((attn_bwd_dq_kernel<D, CAUSAL, false, 1>), g1, 256, 0, s, p, CAUSAL ? -1 : 0);
-  }
-  return 0;
-}
-
-// dK / dV launch: transposing-read ring kernel, round-3 ring kernel on the copies (tools: slam_attn_set_fwd_qf 40), or the register-staged
-// round-1 kernel (variant 1, and every tensor the descriptors cannot address)
-template <int D, bool CAUSAL>
-static int launch_dkdv(const AttnParams& p, int64_t B, hipStream_t s, AttnFits fits) {
-  dim3 gk((unsigned)cdiv64(p.Tk, 64), (unsigned)p.Hkv, (unsigned)B);
-  dim3 gk2((unsigned)cdiv64(p.Tk, 128), (unsigned)p.Hkv, (unsigned)B);
-  if (g_attn_bwd_variant != 1) {
-    if (g_attn_tr && fits.rowmajor) return launch_dkdv_tr<D, CAUSAL>(p, gk2, s);
-    if (!g_attn_tr && fits.rowmajor && fits.copies) return launch_dkdv_ring<D, CAUSAL>(p, gk2, s);
-  }
-  attn_launch((attn_bwd_dkdv_kernel<D, CAUSAL>), gk, 256, 0, s, p, CAUSAL ? 1 : 0);
   return 0;
 }
 
@@ -2524,11 +2531,11 @@ extern "C" int slam_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t 
                              const int32_t* seg_lo, const int32_t* seg_hi, float drop_p, uint64_t drop_seed, const float* rp_gate,
                              const float* rp_tab, int64_t rp_T, int64_t rp_ld, float* rp_ds, float* d_gate, float* d_tab, void* stream) {
   SLAM_CHECK_ARG(Q && K && V && O && dO && LSE && Delta && dQ && dK && dV, "slam_attn_bwd: null pointer");
-  {
-    const int need = slam_attn_needs_transposed(B, Tq, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, (drop_p > 0.f ? 1 : 0) | (rp_gate ? 2 : 0));
-    SLAM_CHECK_ARG(!(need & 2) || (Qt && Kt && dOt), "slam_attn_bwd: this configuration runs the kernels that read the transposed copies: "
-                   "Qt / Kt / dOt must be given (slam_attn_needs_transposed says when)");
-  }
+  const AttnCall c = {true, B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal != 0, true, false, key_mask != nullptr,
+                      seg_lo != nullptr, true, false, rp_gate != nullptr, drop_p > 0.f};
+  const AttnPlan pl = attn_plan(c);
+  SLAM_CHECK_ARG(!pl.reads_copies || (Qt && Kt && dOt), "slam_attn_bwd: this configuration runs the kernels that read the transposed copies: "
+                 "Qt / Kt / dOt must be given (slam_attn_needs_transposed says when)");
   SLAM_CHECK_ARG(!rp_gate || (rp_tab && rp_ds && d_gate && d_tab && D == 64 && !causal && !seg_lo && !rope_cos && Hq == Hkv &&
                               rp_T >= Tq && rp_T >= Tk && rp_ld >= 2 * rp_T - 1),
                  "slam_attn_bwd: the gated relative position bias needs rp_tab / rp_ds / d_gate / d_tab, head_dim 64, bidirectional unpacked MHA "
@@ -2558,63 +2565,37 @@ extern "C" int slam_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t 
   p.drop_salt = g_slam_drop_salt;
   p.rp_gate = rp_gate; p.rp_tab = rp_tab; p.rp_T = (int)rp_T; p.rp_ld = (int)rp_ld; p.rp_ds = rp_ds;
   hipStream_t s = (hipStream_t)stream;
-  const AttnFits fits = attn_fits(B, Tq, Tk, Tqp, Tkp, Hq, Hkv, D, ldq, ldk, ldv, lddo);
-  if (rp_gate) {   // WavLM (unfrozen): the bias joins the recomputed scores; dL/d(score) is materialised once and reduced twice
-    dim3 gq_((unsigned)cdiv64(Tq, 64), (unsigned)Hq, (unsigned)B), gk_((unsigned)cdiv64(Tk, 64), (unsigned)Hkv, (unsigned)B);
-    if (drop_p > 0.f) {     // train-mode attention_dropout: the same mask as the forward, recomputed; dL/d(score) already carries it
-      attn_launch((attn_bwd_dq_kernel<64, false, true, 1, true>), gq_, 256, 0, s, p);
-      attn_launch((attn_bwd_dkdv_kernel<64, false, true, true>), gk_, 256, 0, s, p);
+  int rc = 0;
+  if (pl.rp) {   // WavLM (unfrozen): the bias joins the recomputed scores; dL/d(score) is materialised once and reduced twice
+    if (pl.drop) {     // train-mode attention_dropout: the same mask as the forward, recomputed; dL/d(score) already carries it
+      attn_launch(attn_bwd_dq_kernel<64, false, true, 1, true>, pl.gq, 256, 0, s, p, 0);
+      attn_launch(attn_bwd_dkdv_kernel<64, false, true, true>, pl.gk, 256, 0, s, p, 0);
     } else {
-      attn_launch((attn_bwd_dq_kernel<64, false, false, 1, true>), gq_, 256, 0, s, p);
-      attn_launch((attn_bwd_dkdv_kernel<64, false, false, true>), gk_, 256, 0, s, p);
+      attn_launch(attn_bwd_dq_kernel<64, false, false, 1, true>, pl.gq, 256, 0, s, p, 0);
+      attn_launch(attn_bwd_dkdv_kernel<64, false, false, true>, pl.gk, 256, 0, s, p, 0);
     }
     const int64_t rows = B * Hq * Tq;
     hipLaunchKernelGGL(relpos_dgate_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(rows, 4), 65535 * 4)), dim3(256), 0, s, rp_ds, rp_tab, d_gate, (int)B,
                        (int)Hq, (int)Tq, (int)Tk, (int)Tkp, (int)Tqp, (int)rp_T, (int)rp_ld);
     hipLaunchKernelGGL(relpos_dtab_kernel, dim3((unsigned)cdiv64(2 * rp_T - 1, 256), (unsigned)Hq), dim3(256), 0, s, rp_ds, rp_gate, d_tab, (int)B,
                        (int)Hq, (int)Tq, (int)Tk, (int)Tkp, (int)Tqp, (int)rp_T, (int)rp_ld);
-    SLAM_CHECK_LAUNCH("slam_attn_bwd");
-    return 0;
-  }
-  if (drop_p > 0.f) {   // same mask as the forward, recomputed (round-1 dK/dV kernel: the ring kernel has no dropout form)
-    dim3 gq_((unsigned)cdiv64(Tq, 64), (unsigned)Hq, (unsigned)B), gk_((unsigned)cdiv64(Tk, 64), (unsigned)Hkv, (unsigned)B);
-    attn_launch((attn_bwd_dq_kernel<64, false, true>), gq_, 256, 0, s, p);
-    attn_launch((attn_bwd_dkdv_kernel<64, false, true>), gk_, 256, 0, s, p);
-    SLAM_CHECK_LAUNCH("slam_attn_bwd");
-    return 0;
-  }
-  dim3 gk2((unsigned)cdiv64(Tk, 128), (unsigned)Hkv, (unsigned)B);
-  int rc = 0;
-  if (g_attn_bwd_variant > 10 && D == 128 && causal) {   // timing ablations of the D = 128 causal ring kernel (tools only)
-    SLAM_CHECK_ARG(fits.rowmajor && fits.copies, "slam_attn_bwd: the timing-ablation variants need tensors within the descriptors' 2 GiB");
-    if ((rc = launch_dq<128, true>(p, B, s, fits))) return rc;
-    switch (g_attn_bwd_variant) {
-      case 11: rc = launch_dkdv_ring<128, true, 1>(p, gk2, s); break;
-      case 12: rc = launch_dkdv_ring<128, true, 2>(p, gk2, s); break;
-      case 19: rc = launch_dkdv_ring<128, true, 9>(p, gk2, s); break;
-      case 14: rc = launch_dkdv_ring<128, true, 0>(p, gk2, s); break;
-      default: rc = launch_dkdv_ring<128, true, 5>(p, gk2, s); break;
+  } else if (pl.drop) {   // same mask as the forward, recomputed (round-1 dK/dV kernel: the ring kernel has no dropout form)
+    attn_launch(attn_bwd_dq_kernel<64, false, true>, pl.gq, 256, 0, s, p, 0);
+    attn_launch(attn_bwd_dkdv_kernel<64, false, true>, pl.gk, 256, 0, s, p, 0);
+  } else if (pl.ablation) {
+    SLAM_CHECK_ARG(pl.ok, "slam_attn_bwd: the timing-ablation variants need tensors within the descriptors' 2 GiB");
+    if ((rc = launch_dq<128, true>(pl, p, s))) return rc;
+    switch (pl.abl) {
+      case 1: rc = launch_dkdv_ring<128, true, 1>(pl, p, s); break;
+      case 2: rc = launch_dkdv_ring<128, true, 2>(pl, p, s); break;
+      case 9: rc = launch_dkdv_ring<128, true, 9>(pl, p, s); break;
+      case 0: rc = launch_dkdv_ring<128, true, 0>(pl, p, s); break;
+      default: rc = launch_dkdv_ring<128, true, 5>(pl, p, s); break;
     }
-    if (rc) return rc;
-    SLAM_CHECK_LAUNCH("slam_attn_bwd");
-    return 0;
-  }
-  if (D == 64) {
-    if (causal) {
-      if ((rc = launch_dq<64, true>(p, B, s, fits))) return rc;
-      rc = launch_dkdv<64, true>(p, B, s, fits);
-    } else {
-      if ((rc = launch_dq<64, false>(p, B, s, fits))) return rc;
-      rc = launch_dkdv<64, false>(p, B, s, fits);
-    }
+  } else if (D == 64) {
+    rc = causal ? launch_bwd<64, true>(pl, p, s) : launch_bwd<64, false>(pl, p, s);
   } else {
-    if (causal) {
-      if ((rc = launch_dq<128, true>(p, B, s, fits))) return rc;
-      rc = launch_dkdv<128, true>(p, B, s, fits);
-    } else {
-      if ((rc = launch_dq<128, false>(p, B, s, fits))) return rc;
-      rc = launch_dkdv<128, false>(p, B, s, fits);
-    }
+    rc = causal ? launch_bwd<128, true>(pl, p, s) : launch_bwd<128, false>(pl, p, s);
   }
   if (rc) return rc;
   SLAM_CHECK_LAUNCH("slam_attn_bwd");

@@ -531,6 +531,15 @@ def attn_needs_transposed(q2d, k2d, v2d, do2d, B, T, Tk, Hq, Hkv, D, drop=None, 
     return lib.raw().slam_attn_needs_transposed(B, T, Tk, Hq, Hkv, D, _ld(q2d), _ld(k2d), _ld(v2d), _ld(do2d) if do2d is not None else _ld(q2d), flags)
 
 
+def attn_kernel_name(backward: bool, B, T, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal, present: int) -> str:
+    """the kernels slam_attn_fwd / slam_attn_bwd run for this call under the current knobs (backward: "dQ kernel + dK/dV kernel"):
+    slam_attn_kernel_name, answered by the function that dispatches the launches.  present: the bit mask of include/slam_hip.h"""
+    buf = ctypes.create_string_buffer(160)
+    call("slam_attn_kernel_name", 1 if backward else 0, B, T, Tk, round_up(T, 64), round_up(Tk, 64), Hq, Hkv, D, ldq, ldk, ldv, lddo,
+         1 if causal else 0, present, buf, len(buf))
+    return buf.value.decode()
+
+
 def attn_fwd(q2d, k2d, v, B, T, Hq, Hkv, D, causal, scale, key_mask=None, want_lse=True, out=None, Tk=None, seg=None,
              relpos=None, drop=None, q_prescaled=False):
     """self-attention: q/k/v rows (b*T + t), head h at column h*D.  Cross-attention: pass Tk (key / value rows b*Tk + t).

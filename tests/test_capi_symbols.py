@@ -172,3 +172,139 @@ def test_reset_tuning_replays_the_environment_overrides():
     out = subprocess.run([sys.executable, "-c", child], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     assert out.stdout.strip().splitlines()[-1] == repr(([PIPE, T128x64], [PIPE, T128x64]))
+
+
+# ---- which kernels an attention call runs on: slam_attn_kernel_name / slam_attn_needs_transposed (host code only: no device is touched) ----
+# (slam_attn_set_fwd_qf codes, backward variant, backward, B, Tq, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal, present, kernels, needs_transposed)
+# present: 1 dropout, 2 relative position bias, 4 V row-major, 8 Vt copy, 16 key mask, 32 packed segments, 64 LSE output, 128 pre-scaled Q.
+# Recorded from the commit BEFORE attn_plan() existed, which could not name its kernels: a scratch copy of that attention.hip whose
+# attn_launch stored the kernel it was handed (resolved to its name and template arguments through the symbol table of the recording
+# build) instead of launching it, with the LDS-limit and launch-error calls skipped, driven through slam_attn_fwd / slam_attn_bwd /
+# slam_attn_needs_transposed by ctypes with dummy non-null pointers (nothing is dereferenced on the host); Tqp / Tkp = T rounded up to 64.
+# Rows: both head sizes causal and not, the mask-free and pre-scaled-Q forms and what switches them off (key mask, segments), RP / DROP,
+# V / Vt / both, K and row-major V beyond 2 GiB (the fourth row of that group: QF 2 on register-staged tiles, because the QF rule looks
+# at the K-side copy and the DMA rule at the row-major V), every forward knob and the stamping variant 14; backward: Tq = 64 | 65,
+# dropout / bias / GQA / key mask / segments, row-major operands beyond 2 GiB, the copies beyond 2 GiB under knob 40, variants 1 2 11 12
+# 14 15 19 at D = 128 causal and variants above 10 where they take the normal path, knob 40, cross-attention.
+ATTN_FROZEN = [
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 1, 68, "attn_fwd_kernel<64,true,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 4, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 132, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,true>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 196, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 84, "attn_fwd_kernel<64,false,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 1, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 36, "attn_fwd_kernel<64,false,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 68, "attn_fwd_kernel<128,true,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 0, 68, "attn_fwd_kernel<128,false,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 84, "attn_fwd_kernel<128,true,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 1, 200, 200, 4, 4, 64, 768, 768, 768, 768, 1, 100, "attn_fwd_kernel<64,true,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 70, "attn_fwd_kernel<64,false,2,true,false,false,true,false,true,false>", 2),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 69, "attn_fwd_kernel<64,false,2,false,true,false,true,false,true,false>", 2),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 71, "attn_fwd_kernel<64,false,2,true,true,false,true,false,true,false>", 2),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 72, "attn_fwd_kernel<64,false,2,false,false,false,true,true,false,false>", 0),
+    ((), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 76, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 72, "attn_fwd_kernel<128,true,2,false,false,false,true,false,false,false>", 0),
+    ((), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 76, "attn_fwd_kernel<128,true,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 0, 16, 32768, 32768, 8, 8, 128, 3072, 3072, 3072, 3072, 1, 68, "attn_fwd_kernel<128,true,1,false,false,false,false,false,true,false>", 2),
+    ((), 0, 0, 16, 32768, 32768, 16, 16, 64, 3072, 3072, 3072, 3072, 1, 68, "attn_fwd_kernel<64,true,2,false,false,false,false,false,true,false>", 2),
+    ((), 0, 0, 16, 32768, 32768, 16, 16, 64, 3072, 3072, 3072, 3072, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,false,false,true,false>", 2),
+    ((), 0, 0, 4, 32768, 32768, 8, 8, 128, 1024, 1024, 8192, 1024, 1, 68, "attn_fwd_kernel<128,true,2,false,false,false,false,false,true,false>", 2),
+    ((), 0, 0, 4, 32768, 32768, 8, 8, 128, 1024, 1024, 8192, 1024, 1, 76, "attn_fwd_kernel<128,true,2,false,false,false,false,false,true,false>", 2),
+    ((1,), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 68, "attn_fwd_kernel<128,true,1,false,false,false,true,false,true,false>", 0),
+    ((1,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,1,false,false,false,true,false,true,false>", 0),
+    ((2,), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 68, "attn_fwd_kernel<128,true,2,false,false,false,true,false,true,false>", 0),
+    ((2,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((10,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,false,false,true,false>", 0),
+    ((10,), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 68, "attn_fwd_kernel<128,true,1,false,false,false,false,false,true,false>", 0),
+    ((30,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,true,false,true,false>", 0),
+    ((40,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 3),
+    ((40,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 76, "attn_fwd_kernel<64,false,2,false,false,false,true,true,false,false>", 3),
+    ((40,), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 72, "attn_fwd_kernel<128,true,2,false,false,false,true,false,false,false>", 3),
+    ((40,), 0, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 76, "attn_fwd_kernel<128,true,2,false,false,false,true,false,false,false>", 3),
+    ((60,), 0, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 132, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 14, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 0, 76, "attn_fwd_kernel<64,false,2,false,false,true,true,false,false,false>", 2),
+    ((), 14, 0, 2, 200, 200, 4, 4, 64, 768, 768, 768, 768, 1, 76, "attn_fwd_kernel<64,true,2,false,false,false,true,false,true,false>", 2),
+    ((), 14, 0, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1536, 1, 68, "attn_fwd_kernel<128,true,2,false,false,false,true,false,true,false>", 2),
+    ((), 0, 1, 1, 64, 64, 2, 2, 64, 384, 384, 384, 128, 1, 0, "attn_bwd_dq_kernel<64,true,false,1,false> + attn_bwd_dkdv_tr_kernel<64,true>", 2),
+    ((), 0, 1, 1, 65, 65, 2, 2, 64, 384, 384, 384, 128, 1, 0, "attn_bwd_dq_tr_kernel<64,true,2> + attn_bwd_dkdv_tr_kernel<64,true>", 0),
+    ((), 0, 1, 1, 64, 64, 2, 2, 64, 384, 384, 384, 128, 0, 0, "attn_bwd_dq_kernel<64,false,false,1,false> + attn_bwd_dkdv_tr_kernel<64,false>", 2),
+    ((), 0, 1, 1, 65, 65, 2, 2, 64, 384, 384, 384, 128, 0, 0, "attn_bwd_dq_tr_kernel<64,false,2> + attn_bwd_dkdv_tr_kernel<64,false>", 0),
+    ((), 0, 1, 1, 64, 64, 2, 2, 128, 768, 768, 768, 256, 1, 0, "attn_bwd_dq_kernel<128,true,false,1,false> + attn_bwd_dkdv_tr_kernel<128,true>", 2),
+    ((), 0, 1, 1, 65, 65, 2, 2, 128, 768, 768, 768, 256, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_tr_kernel<128,true>", 0),
+    ((), 0, 1, 1, 64, 64, 2, 2, 128, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_kernel<128,false,false,1,false> + attn_bwd_dkdv_tr_kernel<128,false>", 2),
+    ((), 0, 1, 1, 65, 65, 2, 2, 128, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_tr_kernel<128,false,2> + attn_bwd_dkdv_tr_kernel<128,false>", 0),
+    ((), 0, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 1, "attn_bwd_dq_kernel<64,false,true,1,false> + attn_bwd_dkdv_kernel<64,false,true,false>", 2),
+    ((), 0, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 2, "attn_bwd_dq_kernel<64,false,false,1,true> + attn_bwd_dkdv_kernel<64,false,false,true>", 2),
+    ((), 0, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 3, "attn_bwd_dq_kernel<64,false,true,1,true> + attn_bwd_dkdv_kernel<64,false,true,true>", 2),
+    ((), 0, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_tr_kernel<128,true>", 0),
+    ((), 0, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 16, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_tr_kernel<128,true>", 0),
+    ((), 0, 1, 1, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 32, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_tr_kernel<128,true>", 0),
+    ((), 0, 1, 16, 32768, 32768, 8, 8, 128, 3072, 3072, 3072, 1024, 1, 0, "attn_bwd_dq_kernel<128,true,false,2,false> + attn_bwd_dkdv_kernel<128,true,false,false>", 2),
+    ((), 0, 1, 16, 32768, 32768, 16, 16, 64, 3072, 3072, 3072, 1024, 0, 0, "attn_bwd_dq_kernel<64,false,false,2,false> + attn_bwd_dkdv_kernel<64,false,false,false>", 2),
+    ((40,), 0, 1, 2048, 65, 65, 32, 32, 128, 4096, 4096, 4096, 4096, 1, 0, "attn_bwd_dq_kernel<128,true,false,2,false> + attn_bwd_dkdv_kernel<128,true,false,false>", 3),
+    ((), 0, 1, 2048, 65, 65, 32, 32, 128, 4096, 4096, 4096, 4096, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_tr_kernel<128,true>", 0),
+    ((), 1, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_kernel<128,true,false,1,false> + attn_bwd_dkdv_kernel<128,true,false,false>", 2),
+    ((), 1, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_kernel<64,false,false,1,false> + attn_bwd_dkdv_kernel<64,false,false,false>", 2),
+    ((), 2, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_kernel<128,true,false,2,false> + attn_bwd_dkdv_tr_kernel<128,true>", 2),
+    ((), 2, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_kernel<64,false,false,2,false> + attn_bwd_dkdv_tr_kernel<64,false>", 2),
+    ((), 11, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_ring_kernel<128,true,1>", 2),
+    ((), 12, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_ring_kernel<128,true,2>", 2),
+    ((), 14, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_ring_kernel<128,true,2,true> + attn_bwd_dkdv_ring_kernel<128,true,0>", 2),
+    ((), 15, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_ring_kernel<128,true,5>", 2),
+    ((), 19, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_tr_kernel<128,true,2> + attn_bwd_dkdv_ring_kernel<128,true,9>", 2),
+    ((), 11, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 1, 0, "attn_bwd_dq_tr_kernel<64,true,2> + attn_bwd_dkdv_tr_kernel<64,true>", 2),
+    ((), 12, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 0, 0, "attn_bwd_dq_tr_kernel<128,false,2> + attn_bwd_dkdv_tr_kernel<128,false>", 2),
+    ((), 14, 1, 1, 64, 64, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_kernel<128,true,false,1,false> + attn_bwd_dkdv_ring_kernel<128,true,0>", 2),
+    ((40,), 0, 1, 2, 200, 200, 8, 2, 128, 1536, 1536, 1536, 1024, 1, 0, "attn_bwd_dq_ring_kernel<128,true,2,false> + attn_bwd_dkdv_ring_kernel<128,true,0>", 3),
+    ((40,), 0, 1, 2, 200, 200, 4, 4, 64, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_ring_kernel<64,false,2,false> + attn_bwd_dkdv_ring_kernel<64,false,0>", 3),
+    ((40,), 0, 1, 1, 64, 64, 4, 4, 64, 768, 768, 768, 256, 0, 0, "attn_bwd_dq_kernel<64,false,false,1,false> + attn_bwd_dkdv_ring_kernel<64,false,0>", 3),
+    ((), 0, 0, 2, 100, 300, 4, 4, 64, 256, 512, 512, 256, 0, 68, "attn_fwd_kernel<64,false,2,false,false,false,true,true,true,false>", 0),
+    ((), 0, 0, 2, 100, 300, 8, 8, 128, 1024, 2048, 2048, 1024, 0, 84, "attn_fwd_kernel<128,false,2,false,false,false,true,false,true,false>", 0),
+    ((), 0, 1, 2, 100, 300, 4, 4, 64, 256, 512, 512, 256, 0, 0, "attn_bwd_dq_tr_kernel<64,false,2> + attn_bwd_dkdv_tr_kernel<64,false>", 0),
+    ((), 0, 1, 2, 100, 300, 8, 8, 128, 1024, 2048, 2048, 1024, 0, 0, "attn_bwd_dq_tr_kernel<128,false,2> + attn_bwd_dkdv_tr_kernel<128,false>", 0),
+    ((), 0, 1, 2, 40, 300, 4, 4, 64, 256, 512, 512, 256, 0, 0, "attn_bwd_dq_kernel<64,false,false,1,false> + attn_bwd_dkdv_tr_kernel<64,false>", 2),
+]
+
+
+def attn_row_mismatches(rows, set_knobs=True):
+    from slam_llm_amd import lib, ops
+    bad = []
+    for knobs, variant, bwd, B, Tq, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal, present, want, want_needs in rows:
+        if set_knobs:
+            lib.call("slam_reset_tuning")
+            for k in knobs:
+                lib.call("slam_attn_set_fwd_qf", k)
+            lib.call("slam_attn_set_bwd_variant", variant)
+        got = ops.attn_kernel_name(bwd, B, Tq, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, causal, present)
+        needs = lib.raw().slam_attn_needs_transposed(B, Tq, Tk, Hq, Hkv, D, ldq, ldk, ldv, lddo, present & 3)
+        # variants 0 1 2 (production, the suite, ops.attn_bwd) and the knobs: the recorded answer.  The tools' variants above 10 used to
+        # ask for Qt / Kt / dOt whatever ran; the answer may narrow to what the planned kernels read, never widen
+        needs_ok = needs == want_needs if variant <= 2 else (needs & 2) <= (want_needs & 2)
+        if got != want or not needs_ok:
+            bad.append((knobs, variant, bwd, B, Tq, Tk, D, causal, present, got, want, needs, want_needs))
+    return bad
+
+
+def test_attn_kernel_labels_did_not_move():
+    from slam_llm_amd import ops
+    assert len(ATTN_FROZEN) >= 60 and len(set(r[:15] for r in ATTN_FROZEN)) == len(ATTN_FROZEN)
+    assert len(set(r[15] for r in ATTN_FROZEN)) >= 40      # (that many different launches are pinned)
+    try:
+        assert attn_row_mismatches(ATTN_FROZEN) == []
+    finally:
+        ops.reset_tuning()
+
+
+def test_reset_tuning_restores_the_attention_defaults():
+    from slam_llm_amd import lib, ops
+    defaults = [r for r in ATTN_FROZEN if r[0] == () and r[1] == 0]
+    assert len(defaults) >= 40
+    try:
+        for code in (1, 10, 20, 30, 40, 50, 60):
+            lib.call("slam_attn_set_fwd_qf", code)
+        lib.call("slam_attn_set_bwd_variant", 2)
+        assert len(attn_row_mismatches(defaults, set_knobs=False)) >= 20     # (the knobs are felt)
+        ops.reset_tuning()
+        assert attn_row_mismatches(defaults, set_knobs=False) == []
+    finally:
+        ops.reset_tuning()

@@ -844,6 +844,8 @@ def test_attention_fwd_prescaled_q_tail_discards_neighbour_keys(dev, T):
     (2, 100, 4, 2, 64, True),
     (2, 380, 4, 1, 128, True),
     (1, 70, 2, 2, 128, False),
+    (1, 64, 2, 1, 64, False),      # both sides of the dQ boundary: <= 64 queries stay on the register-staged dQ kernel ...
+    (1, 65, 2, 1, 128, False),     # ... one more takes the 128-query transposed-read (or ring) form
 ])
 def test_attention_bwd(dev, attn_form, B, T, Hq, Hkv, D, masked):
     ops = _ops()
